@@ -24,19 +24,29 @@ call -- and exits with the worst rank's status; rank 0's line is the output.
 A --gpus that disagrees with WORLD_SIZE, or more ranks than visible GPUs
 (outside a CE_AMD_REHEARSAL=1 rehearsal), exits 2 without a line.
 
+A plain run sets up, warms up, times --steps steps and prints the line; the
+checks and baselines that take work of their own run only with --full (without
+it selected_equal_n1, selected_check and cpu_baseline are null).
+
+--dump-outputs DIR writes what the last timed step returned, after the timed
+region: DIR/values.npy (the q entropies, float64) and DIR/indices.npy (the q
+selected pool positions, best first, as float64: exact below 2^53).  The pool
+is seeded, so two builds run with the same arguments compare file for file.
+
 Also reported:
   ranks / backend  the process group's size and backend (None at N=1)
-  selected_equal_n1  the merged selection equals the N=1 selection of the same
-                pool: rank 0 re-selects the whole pool after the timed region
-                on its GPU by the chunked single-GPU path (ops.MCChunkJob), and
-                compares with the committed 1-GPU record (profiles/
-                selected_n1.json) when there is one; a mismatch exits 3
   roofline      the selection kernel (stage 1 + folded stage 2): algorithmic
                 bytes (N_local x 256 B) / its mean duration from HIP events on
                 the launch stream, vs 8 TB/s;
                 traffic = HBM bytes per launch from the committed rocprofv3 PMC
                 pass (profiles/traffic.json) of the kernel this run launched
                 (ce_last_kernel()), or null when that record names another
+With --full:
+  selected_equal_n1  the merged selection equals the N=1 selection of the same
+                pool: rank 0 re-selects the whole pool after the timed region
+                on its GPU by the chunked single-GPU path (ops.MCChunkJob), and
+                compares with the committed 1-GPU record (profiles/
+                selected_n1.json) when there is one; a mismatch exits 3
   cpu_baseline  the reference's own expressions (amg_test.py:441-445, numpy +
                 scipy) on a bounded sample, rank 0 at N=1 only
 """
@@ -395,7 +405,14 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=6_000_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-n1-check", action="store_true", help="skip the N=1 re-selection of the pool")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check the selection against the N=1 selection of the pool "
+                         "and measure the CPU baseline (--cpu-sample, --no-cpu-baseline, --no-n1-check apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's (vals, idx) as DIR/values.npy and DIR/indices.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     # before ANY GPU call: a plain `python3 bench.py --gpus N` starts N ranks itself
     mode, world = launch_plan(args.gpus, os.environ, torch.cuda.device_count())
@@ -475,18 +492,24 @@ def main():
         elapsed = t.item()
     kern_ms = statistics.mean(a.elapsed_time(b) for a, b in ev)
     picks = idx.cpu().tolist()
+    if args.dump_outputs and rank == 0:  # every rank holds the same merged (vals, idx)
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "values.npy"), vals.cpu().numpy().astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "indices.npy"), idx.cpu().numpy().astype(np.float64))
     launched = ce_amd._lib.load().ce_last_kernel().decode()  # the stage-1 kernel of the last step
     backend = dist.get_backend() if world > 1 else None
 
     bytes_per_launch = n_local * M * C * P.element_size()
-    # release the pool before the checks below (the N=1 re-selection and the
-    # CPU baseline): only the selected positions are needed from here on
+    # release the pool before the --full checks below (the N=1 re-selection and
+    # the CPU baseline): only the selected positions are needed from here on
     del step, P
     plan = sstep = None  # noqa: F841
     torch.cuda.empty_cache()
 
     check = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # the ranks' merged selection vs the N=1 selection of the same pool
         # (after the timed region): the committed 1-GPU record when there is
         # one for this workload, and a re-selection on this GPU by the chunked
@@ -501,6 +524,9 @@ def main():
                            "through ops.MCChunkJob (one GPU, one running top-q), after the timed region"}
 
     if rank == 0:
+        equal_n1 = None  # without --full, or with neither a re-selection nor a record
+        if check is not None and (check["n1_rechecked"] is not None or check["n1_record"] is not None):
+            equal_n1 = check["n1_rechecked"] is not False and check["n1_record"] is not False
         achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
         traffic, traffic_src = recorded_traffic(f"{args.layout}_{N}_{M}_{C}_q{q}_w{world}", launched)
         line = {
@@ -539,15 +565,14 @@ def main():
             "ranks": world,
             "backend": backend,
             "selected": picks,
-            "selected_equal_n1": (None if check["n1_rechecked"] is None and check["n1_record"] is None
-                                  else check["n1_rechecked"] is not False and check["n1_record"] is not False),
+            "selected_equal_n1": equal_n1,
             "selected_check": check,
         }
         if rehearsal:  # ranks sharing one GPU over gloo: a code-path rehearsal, not a multi-GPU figure
             line["rehearsal"] = {"backend": "gloo", "gpus_visible": torch.cuda.device_count(),
                                  "note": "NOT a multi-GPU measurement"}
             line["value"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample, M, C, q)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -104,10 +104,11 @@ def test_rccl_step_graph_world1():
         dist.destroy_process_group()
 
 
-def test_bench_contract_small():
-    """bench.py's JSON line (the driver's contract) on a small pool: the
+def test_bench_contract_small(tmp_path):
+    """bench.py --full's JSON line (the driver's contract) on a small pool: the
     required keys, roofline / cpu_baseline objects, and a selection that
-    equals the oracle's on the same synthetic pool."""
+    equals the oracle's on the same synthetic pool; --dump-outputs writes that
+    selection as float64 arrays."""
     import json
     import subprocess
     import sys
@@ -117,10 +118,13 @@ def test_bench_contract_small():
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n-items", "2000000", "--steps", "3",
-                        "--warmup", "1", "--cpu-sample", "200000"], capture_output=True, text=True, timeout=600,
-                       env=env)
+                        "--warmup", "1", "--cpu-sample", "200000", "--full", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
+    vals, idx = np.load(tmp_path / "out" / "values.npy"), np.load(tmp_path / "out" / "indices.npy")
+    assert vals.dtype == idx.dtype == np.float64 and vals.shape == idx.shape == (10,)
+    assert idx.tolist() == line["selected"] and np.all(np.diff(vals) <= 0) and np.all(vals > 0)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in line, k
@@ -133,6 +137,30 @@ def test_bench_contract_small():
     assert line["ranks"] == 1 and line["selected_equal_n1"] is True
     assert line["selected_check"]["n1_rechecked"] is True and line["selected_check"]["n1_record"] is None
     assert cb["kind"] == "reference"
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """Without --full the bench times its steps and prints the line: no N=1
+    re-selection, no CPU baseline; --steps sets the timed steps, ms_per_step is
+    one of them, and the dumped selection is the line's."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--n-items", "2000000",
+                        "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["unit"] == "items/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(2000000 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["cpu_baseline"] is None and line["selected_equal_n1"] is None and line["selected_check"] is None
+    assert 0 < line["roofline"]["kernel_ms"] <= line["ms_per_step"]
+    assert sorted(os.listdir(tmp_path)) == ["indices.npy", "values.npy"]
+    assert np.load(tmp_path / "indices.npy").tolist() == line["selected"]
 
 
 def test_rccl_sharded_mix_and_batched_world1():
@@ -191,7 +219,7 @@ def test_bench_world2_rehearsal():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    args = ["bench.py", "--steps", "3", "--warmup", "1", "--n-items", "3000001", "--no-cpu-baseline"]
+    args = ["bench.py", "--steps", "3", "--warmup", "1", "--n-items", "3000001", "--full", "--no-cpu-baseline"]
     one = subprocess.run([sys.executable] + args, cwd=root, capture_output=True, text=True, timeout=600, env=env)
     assert one.returncode == 0, one.stderr[-2000:]
     env2 = dict(env, CE_AMD_REHEARSAL="1")

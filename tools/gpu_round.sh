@@ -44,7 +44,7 @@ check)
   step $? pytest
   timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
   step $? smoke
-  bench nmc python bench.py ${BENCH_ARGS}
+  bench nmc python bench.py --full ${BENCH_ARGS}
   for v in ${AB}; do  # AB="name:ENV=val,ENV2=val:args ..."
     IFS=: read -r n e a <<< "$v"
     bench "$n" ${e//,/ } python bench.py --no-cpu-baseline ${a//\%/ }
