@@ -210,8 +210,9 @@ def reserve_graph_workspace(nbytes, device=None):
         WORKSPACE.arena.reserve(device, int(nbytes))
 
 
-def committee_view(P, layout="MNC"):
-    """(N, M, C, sN, sM, sC, dtype code) of a committee tensor.  'MNC' is the
+def _committee_args(P, layout):
+    """The committee run of the C-ABI's signatures, to splat into a call:
+    (p, dtype code, N, M, C, sN, sM, sC) of a committee tensor.  'MNC' is the
     reference's stack np.array(pred_prob) (amg_test.py:441); 'NMC' is the
     item-major [N, M, C] tensor.  Any strides are accepted."""
     _on_gpu(P, "committee")
@@ -229,55 +230,67 @@ def committee_view(P, layout="MNC"):
         raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
     if M < 1 or C < 1:
         raise ValueError(f"committee needs M >= 1 members and C >= 1 classes, got M={M}, C={C}")
-    return N, M, C, sN, sM, sC, _DT[P.dtype]
+    return _p(P), _DT[P.dtype], N, M, C, sN, sM, sC
+
+
+def committee_view(P, layout="MNC"):
+    """(N, M, C, sN, sM, sC, dtype code) of a committee tensor ('MNC' / 'NMC', any strides)."""
+    _, dt, N, M, C, sN, sM, sC = _committee_args(P, layout)
+    return N, M, C, sN, sM, sC, dt
 
 
 def committee_entropy(P, layout="MNC", return_mean=False):
     """amg_test.py:441+443 per item: f64 entropies [N] (and the [N, C] mean)."""
-    N, M, C, sN, sM, sC, dt = committee_view(P, layout)
+    comm = _committee_args(P, layout)
+    N, C = comm[2], comm[4]
     ent = torch.empty(N, dtype=torch.float64, device=P.device)
     mean = torch.empty((N, C), dtype=torch.float64, device=P.device) if return_mean else None
-    call("ce_committee_entropy", _p(P), dt, N, M, C, sN, sM, sC, _p(mean), _p(ent), _stream(P.device))
+    call("ce_committee_entropy", *comm, _p(mean), _p(ent), _stream(P.device))
     return (ent, mean) if return_mean else ent
+
+
+def _map_f64(fn, name, x):
+    """y[i] = fn(x[i]) over a float64 device tensor (ce_log_f64 / ce_exp_f64)."""
+    _on_gpu(x, "x")
+    x = x.contiguous()
+    if x.dtype != torch.float64:
+        raise ValueError(f"{name} takes float64")
+    y = torch.empty_like(x)
+    call(fn, _p(x), x.numel(), _p(y), _stream(x.device))
+    return y
 
 
 def log_f64(x):
     """glibc's log(x) as the engine evaluates it inside every entropy
     (ce_log_f64; verification against the C library)."""
-    _on_gpu(x, "x")
-    x = x.contiguous()
-    if x.dtype != torch.float64:
-        raise ValueError("log_f64 takes float64")
-    y = torch.empty_like(x)
-    call("ce_log_f64", _p(x), x.numel(), _p(y), _stream(x.device))
-    return y
+    return _map_f64("ce_log_f64", "log_f64", x)
 
 
 def exp_f64(x):
     """glibc's exp(x) as the engine evaluates it in the GaussianNB member
     (ce_exp_f64; verification against the C library)."""
-    _on_gpu(x, "x")
-    x = x.contiguous()
-    if x.dtype != torch.float64:
-        raise ValueError("exp_f64 takes float64")
-    y = torch.empty_like(x)
-    call("ce_exp_f64", _p(x), x.numel(), _p(y), _stream(x.device))
-    return y
+    return _map_f64("ce_exp_f64", "exp_f64", x)
+
+
+def _approx_rows(fn, name, rows, dtype=None):
+    """(h2 f32 [n], special bool [n]) of rows [n, C] f64 through ce_approx_entropy /
+    ce_wide_approx_entropy (dtype: the latter's committee dtype)."""
+    _on_gpu(rows, "rows")
+    rows = rows.contiguous()
+    if rows.dtype != torch.float64 or rows.dim() != 2:
+        raise ValueError(f"{name} takes [n, C] float64")
+    n, C = rows.shape
+    h2 = torch.empty(n, dtype=torch.float32, device=rows.device)
+    sp = torch.empty(n, dtype=torch.uint8, device=rows.device)
+    call(fn, _p(rows), n, C, *(() if dtype is None else (_DT[dtype],)), _p(h2), _p(sp), _stream(rows.device))
+    return h2, sp.bool()
 
 
 def approx_entropy(rows):
     """The single-block pools' approximate entropy of exact consensus rows
     [n, C] f64 (ce_approx_entropy: log2 units, f32) and their special flags
     (verification of the prefilter's error bound)."""
-    _on_gpu(rows, "rows")
-    rows = rows.contiguous()
-    if rows.dtype != torch.float64 or rows.dim() != 2:
-        raise ValueError("approx_entropy takes [n, C] float64")
-    n, C = rows.shape
-    h2 = torch.empty(n, dtype=torch.float32, device=rows.device)
-    sp = torch.empty(n, dtype=torch.uint8, device=rows.device)
-    call("ce_approx_entropy", _p(rows), n, C, _p(h2), _p(sp), _stream(rows.device))
-    return h2, sp.bool()
+    return _approx_rows("ce_approx_entropy", "approx_entropy", rows)
 
 
 def wide_approx_entropy(rows, dtype=torch.bfloat16):
@@ -285,15 +298,7 @@ def wide_approx_entropy(rows, dtype=torch.bfloat16):
     log2 units, f32) of rows [n, C] f64 -- member sums or means, in the register
     layout k_stream_wide2 uses for a ``dtype`` committee -- and their special
     flags (verification of the margin the C5 prefilter skips items by)."""
-    _on_gpu(rows, "rows")
-    rows = rows.contiguous()
-    if rows.dtype != torch.float64 or rows.dim() != 2:
-        raise ValueError("wide_approx_entropy takes [n, C] float64")
-    n, C = rows.shape
-    h2 = torch.empty(n, dtype=torch.float32, device=rows.device)
-    sp = torch.empty(n, dtype=torch.uint8, device=rows.device)
-    call("ce_wide_approx_entropy", _p(rows), n, C, _DT[dtype], _p(h2), _p(sp), _stream(rows.device))
-    return h2, sp.bool()
+    return _approx_rows("ce_wide_approx_entropy", "wide_approx_entropy", rows, dtype)
 
 
 def row_div_f64(x, s):
@@ -595,18 +600,18 @@ def select_mc(P, q, layout="MNC", base_idx=0, excl=None):
     """Fused amg_test.py:441-445: (vals [q], idx [q]) best-first.  excl: an
     optional exclusion bitmap (int32 [ceil(N/32)], bit i set = item i is out
     of the pool), see excl_bitmap / mark_selected."""
-    N, M, C, sN, sM, sC, dt = committee_view(P, layout)
+    comm = _committee_args(P, layout)
+    N = comm[2]
     q = _check_q(q)
     lib = _lib.load()
     ws = WORKSPACE.get(P.device, lib.ce_select_mc_workspace_bytes(N, q), _sort_path(q))
     vals, idx = _outs(q, P.device)
     if excl is None:
-        call("ce_select_mc", _p(P), dt, N, M, C, sN, sM, sC, q, int(base_idx), _p(ws), ws.numel(), _p(vals),
-             _p(idx), _stream(P.device))
+        call("ce_select_mc", *comm, q, int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx), _stream(P.device))
     else:
         _check_excl(excl, N)
-        call("ce_select_mc_excl", _p(P), dt, N, M, C, sN, sM, sC, _p(excl), q, int(base_idx), _p(ws), ws.numel(),
-             _p(vals), _p(idx), _stream(P.device))
+        call("ce_select_mc_excl", *comm, _p(excl), q, int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx),
+             _stream(P.device))
     return vals, idx
 
 
@@ -639,7 +644,8 @@ class MCPlan:
 
     def __init__(self, P, q, layout="NMC", base_idx=0):
         self.P = P
-        self.N, self.M, self.C, self.sN, self.sM, self.sC, self.dt = committee_view(P, layout)
+        self.comm = _committee_args(P, layout)  # every launch splats it
+        _, self.dt, self.N, self.M, self.C, self.sN, self.sM, self.sC = self.comm
         self.q = _check_q(q)
         self.base_idx = int(base_idx)
         lib = _lib.load()
@@ -648,8 +654,8 @@ class MCPlan:
         self.vals, self.idx = _outs(self.q, P.device)
 
     def partial(self):
-        call("ce_select_mc_partial", _p(self.P), self.dt, self.N, self.M, self.C, self.sN, self.sM, self.sC, self.q,
-             self.base_idx, _p(self.ws), self.ws_bytes, _stream(self.P.device))
+        call("ce_select_mc_partial", *self.comm, self.q, self.base_idx, _p(self.ws), self.ws_bytes,
+             _stream(self.P.device))
 
     def finish(self):
         call("ce_select_finish", self.N, self.q, _p(self.ws), self.ws_bytes, _p(self.vals), _p(self.idx),
@@ -668,8 +674,8 @@ class MCPlan:
     def step(self):
         """The whole selection (ce_select_mc; ONE launch for q <= 64: stage 2
         folded into stage 1's last block): (vals [q], idx [q])."""
-        call("ce_select_mc", _p(self.P), self.dt, self.N, self.M, self.C, self.sN, self.sM, self.sC, self.q,
-             self.base_idx, _p(self.ws), self.ws_bytes, _p(self.vals), _p(self.idx), _stream(self.P.device))
+        call("ce_select_mc", *self.comm, self.q, self.base_idx, _p(self.ws), self.ws_bytes, _p(self.vals),
+             _p(self.idx), _stream(self.P.device))
         return self.vals, self.idx
 
     def step_cands(self, out=None):
@@ -677,8 +683,8 @@ class MCPlan:
         buffer; ce_select_mc_cands, ONE launch for q <= 64)."""
         if out is None:
             out = torch.empty((self.q, 2), dtype=torch.int64, device=self.P.device)
-        call("ce_select_mc_cands", _p(self.P), self.dt, self.N, self.M, self.C, self.sN, self.sM, self.sC, self.q,
-             self.base_idx, _p(self.ws), self.ws_bytes, _p(out), _stream(self.P.device))
+        call("ce_select_mc_cands", *self.comm, self.q, self.base_idx, _p(self.ws), self.ws_bytes, _p(out),
+             _stream(self.P.device))
         return out
 
     def __call__(self):
@@ -723,7 +729,8 @@ class MCChunkJob:
     def add(self, P, base_idx=None):
         """Score chunk P (layout as constructed); its items are pool positions
         base_idx .. base_idx + N - 1 (default: right after the previous chunk)."""
-        N, M, C, sN, sM, sC, dt = committee_view(P, self.layout)
+        comm = _committee_args(P, self.layout)
+        N = comm[2]
         if self.running is None:
             if self.device is not None and self.device.index is not None and P.device != self.device:
                 raise ValueError(f"chunk on {P.device}, job on {self.device}")
@@ -741,8 +748,8 @@ class MCChunkJob:
         lib = _lib.load()
         ws = WORKSPACE.get(P.device, lib.ce_select_mc_chunk_workspace_bytes(N, self.q), _sort_path(self.q))
         first = 1 if self._fresh else 0
-        call("ce_select_mc_chunk", _p(P), dt, N, M, C, sN, sM, sC, self.q, base, _p(self.running), first, _p(ws),
-             ws.numel(), _stream(P.device))
+        call("ce_select_mc_chunk", *comm, self.q, base, _p(self.running), first, _p(ws), ws.numel(),
+             _stream(P.device))
         self._fresh = False
         self.n_items = max(self.n_items, base + N)
         return self
@@ -781,7 +788,8 @@ def select_mc_chunks(chunks, q, layout="NMC"):
 
 def select_mix(P, hc, q, layout="MNC"):
     """Fused amg_test.py:473-480: top-q over the row stack [mc (N); hc (N_h)]."""
-    N, M, C, sN, sM, sC, dt = committee_view(P, layout)
+    comm = _committee_args(P, layout)
+    N, C = comm[2], comm[4]
     _on_gpu(hc, "hc table")
     if hc.dim() != 2 or hc.shape[1] != C:
         raise ValueError(f"hc table must be [N_h, {C}]")
@@ -793,15 +801,16 @@ def select_mix(P, hc, q, layout="MNC"):
     lib = _lib.load()
     ws = WORKSPACE.get(P.device, lib.ce_select_mix_workspace_bytes(N, N_h, q), _sort_path(q))
     vals, idx = _outs(q, P.device)
-    call("ce_select_mix", _p(P), dt, N, M, C, sN, sM, sC, _p(hc), N_h, hc.stride(0), q, _p(ws), ws.numel(),
-         _p(vals), _p(idx), _stream(P.device))
+    call("ce_select_mix", *comm, _p(hc), N_h, hc.stride(0), q, _p(ws), ws.numel(), _p(vals), _p(idx),
+         _stream(P.device))
     return vals, idx
 
 
 def select_batched(P, offsets, q, layout="MNC"):
     """U users in one launch; user u owns items offsets[u]:offsets[u+1].
     Returns (vals [U, q], idx [U, q]) with user-local positions."""
-    N, M, C, sN, sM, sC, dt = committee_view(P, layout)
+    comm = _committee_args(P, layout)
+    N = comm[2]
     _on_gpu(offsets, "offsets")
     offsets = offsets.to(torch.int64).contiguous()
     U = offsets.numel() - 1
@@ -811,6 +820,5 @@ def select_batched(P, offsets, q, layout="MNC"):
     lib = _lib.load()
     ws = WORKSPACE.get(P.device, lib.ce_select_batched_workspace_bytes(N, U, q), _sort_path(q))
     vals, idx = _outs(q, P.device, (U,))
-    call("ce_select_batched", _p(P), dt, N, M, C, sN, sM, sC, _p(offsets), U, q, _p(ws), ws.numel(), _p(vals),
-         _p(idx), _stream(P.device))
+    call("ce_select_batched", *comm, _p(offsets), U, q, _p(ws), ws.numel(), _p(vals), _p(idx), _stream(P.device))
     return vals, idx

@@ -7,12 +7,9 @@
 using namespace ce;
 
 // q <= 64: the streaming kernels' lists; 64 < q <= CE_MAX_Q: the lists of the
-// entropy vector's selection + the N entropies behind them; q > CE_MAX_Q: the sort path.
-extern "C" size_t ce_select_frames_workspace_bytes(int64_t N, int32_t q) {
-    if (q > CE_MAX_Q) return sort_ws_bytes(N);
-    const size_t lists = lists_bytes(pool_blocks(N), q < 1 ? 1 : q);
-    return q > kStreamMaxQ ? lists + 256 + (size_t)(N > 0 ? N : 0) * 8 : lists;
-}
+// entropy vector's selection + the N entropies behind them; q > CE_MAX_Q: the
+// sort path (ws_frames, ce_ws.hpp).
+extern "C" size_t ce_select_frames_workspace_bytes(int64_t N, int32_t q) { return ws_frames(N, q).bytes; }
 
 extern "C" int ce_select_frames(const ce_member* members, int32_t M, int32_t C, const int64_t* offsets,
                                 const int64_t* perm_or_null, int64_t N, int32_t q, int64_t base_idx, void* ws,
@@ -24,7 +21,9 @@ extern "C" int ce_select_frames(const ce_member* members, int32_t M, int32_t C, 
         return fail(CE_EINVAL, "bad frame selection arguments");
     if (C != 2 && C != 3 && C != 4 && C != 8) return fail(CE_EUNSUPPORTED, "frame selection: C=%d not in {2, 3, 4, 8}", C);
     const int G = pool_blocks(N);
-    if (!ws || ws_bytes < ce_select_frames_workspace_bytes(N, q)) return fail(CE_EWORKSPACE, "workspace too small");
+    const WsLayout L = ws_frames(N, q);
+    rc = check_ws(L, ws, ws_bytes);
+    if (rc) return rc;
     FrameArgs fa{};
     for (int m = 0; m < M; ++m) {
         const ce_member& x = members[m];
@@ -44,21 +43,14 @@ extern "C" int ce_select_frames(const ce_member* members, int32_t M, int32_t C, 
     fa.pow2 = (M & (M - 1)) == 0;
     fa.base_idx = base_idx;
     fa.nlists = G;
-    hipStream_t st = (hipStream_t)stream;
-    note_kernel("%s", "");
+    const hipStream_t st = enter(stream);
     if (q == 0) return CE_OK;
     if (q > kStreamMaxQ) {  // per-song entropies to HBM, then the lists (q <= CE_MAX_Q) or the sort path
-        double* ent;
-        SortWs s{};
         if (q > CE_MAX_Q) {
-            const int rc = check_sort_n(N);
+            rc = check_sort_n(N);
             if (rc) return rc;
-            s = sort_carve(ws, N);
-            ent = s.ent;
-        } else {
-            const WsLists wl = carve(ws, G, q);
-            ent = reinterpret_cast<double*>(((uintptr_t)(wl.c + (int64_t)G * q) + 255) & ~(uintptr_t)255);
         }
+        double* ent = ws_ptr<double>(ws, L.ent);
         if (N > 0) {
             const int eg = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(N, 256), 8192));
             switch (C) {
@@ -67,17 +59,10 @@ extern "C" int ce_select_frames(const ce_member* members, int32_t M, int32_t C, 
 #undef CE_FE
             }
         }
-        if (q > CE_MAX_Q) {
-            sort_select(s, ent, N, base_idx, nullptr, q, val_out, idx_out, nullptr, st);
-        } else {
-            WsLists w = carve(ws, G, q);
-            Seg sg{nullptr, N, G, base_idx};
-            partial_entropies(ent, sg, G, q, w, val_out, idx_out, G == 1, st);
-            if (G > 1) finish_lists(w, 1, G, q, val_out, idx_out, st);
-        }
+        select_entropies(L, ws, ent, N, q, base_idx, val_out, idx_out, st);
         return check_launch("ce_select_frames");
     }
-    WsLists w = carve(ws, G, q);
+    const WsLists w = lists_view(L, ws);
     fa.ctr = w.ctr;
     fa.oval = val_out;
     fa.oidx = idx_out;

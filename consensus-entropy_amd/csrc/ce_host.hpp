@@ -1,5 +1,6 @@
 // ce_host.hpp -- host side shared by the C-ABI translation units: argument
-// checks, workspace geometry, dispatch helpers, and the declarations of the
+// checks, typed views of the workspace layout (ce_ws.hpp), dispatch helpers,
+// the selection tails every entry point shares, and the declarations of the
 // launchers (each defined in one ce_launch_*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,39 +16,40 @@
 #include "ce_abi.hpp"
 #include "ce_kernels.hpp"
 #include "ce_sort.hpp"
+#include "ce_ws.hpp"
 
 using namespace ce;
 
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// ---- workspace views ---------------------------------------------------------
+// ce_ws.hpp holds the layout (sizes and region offsets, one WsLayout per entry
+// point); these put device types on its regions.  A region is reached only
+// through the layout whose `bytes` the entry point checked (check_ws).
+static_assert(sizeof(Cand) == kCandBytes, "ce_ws.hpp sizes the lists in Cand records");
 
-// stage-1 blocks for a pool of n items (host arithmetic only: ws sizing and
-// launches agree by construction)
-static inline int pool_blocks(int64_t n) {
-    // one 64-item tile per wave at least; up to 1024 blocks (4 per CU), so wide
-    // items (tens of KB each) still fill the chip
-    int64_t g = cdiv(n, (int64_t)kMinItemsPerBlock);
-    if (g < 1) g = 1;
-    if (g > kMaxBlocks) g = kMaxBlocks;
-    return (int)g;
+template <class T>
+static inline T* ws_ptr(void* ws, Region r) {
+    return reinterpret_cast<T*>(ws_base(ws) + r.off);
 }
 
-// Workspace layout (every *_workspace_bytes / carve agree): a fixed header of
-// kWsCounters u32 arrival counters (the tiled kernels' tickets, one per
-// problem; zero at rest: the caller zero-fills the workspace once, every call
-// leaves the counters zero) followed by the candidate lists, 16 B per slot.
-// The header is the same for every entry point, so one workspace can serve
-// any sequence of calls.
-constexpr int kWsCounters = 16384;
-constexpr size_t kWsHeader = (size_t)kWsCounters * sizeof(uint32_t);  // 64 KiB
-static inline size_t lists_bytes(int64_t nlists, int q) {
-    return kWsHeader + (size_t)nlists * (size_t)q * 16u + 256u;
+static inline int check_ws(const WsLayout& L, const void* ws, size_t ws_bytes) {
+    if (!ws || ws_bytes < L.bytes) return fail(CE_EWORKSPACE, "workspace too small");
+    return CE_OK;
 }
 
-// The wide stream's floor + grid vote scratch (k_wide_seed / k_wide_seed_pick),
-// carved right after a launch's lists: every workspace size that can reach a
-// folded wide launch adds kWideSeedBytes (ce_topq_workspace_bytes,
-// ce_select_mc_chunk_workspace_bytes).
-constexpr size_t kWideSeedBytes = 256 + 256 + (size_t)kWideVoteSamples * (sizeof(Cand) + sizeof(float)) + 256;
+struct WsLists {
+    Cand* c;        // candidate lists
+    uint32_t* ctr;  // arrival counters (header)
+};
+static inline WsLists lists_view(const WsLayout& L, void* ws) {
+    return WsLists{ws_ptr<Cand>(ws, L.lists), ws_ptr<uint32_t>(ws, L.ctr)};
+}
+
+static inline SortWs sort_view(const WsLayout& L, void* ws) {
+    return SortWs{ws_ptr<double>(ws, L.ent),    ws_ptr<Cand>(ws, L.a),        ws_ptr<Cand>(ws, L.b),
+                  ws_ptr<uint32_t>(ws, L.hist), ws_ptr<uint64_t>(ws, L.dtot), ws_ptr<Cand>(ws, L.extra), L.g};
+}
+
+// The wide stream's floor + grid vote scratch (a layout's `seed` region)
 constexpr int64_t kWideSeedMinItems = 16 * 1024;  // >= 1024 samples (wide_nsamples: 1/16 of the items)
 struct WideSeedWs {
     uint32_t* vote;
@@ -55,28 +57,17 @@ struct WideSeedWs {
     Cand* samp;   // [kWideVoteSamples]
     float* sapx;  // [kWideVoteSamples]
 };
-static inline WideSeedWs wide_seed_carve(void* base) {
-    const uintptr_t p = ((uintptr_t)base + 255) & ~(uintptr_t)255;
-    WideSeedWs w;
-    w.vote = reinterpret_cast<uint32_t*>(p);
-    w.seed = reinterpret_cast<Cand*>(p + 16);
-    w.samp = reinterpret_cast<Cand*>(p + 256);
-    w.sapx = reinterpret_cast<float*>(p + 256 + (size_t)kWideVoteSamples * sizeof(Cand));
-    return w;
+static inline WideSeedWs wide_seed_carve(void* seed_region) {
+    const uintptr_t p = ws_base(seed_region);
+    return WideSeedWs{reinterpret_cast<uint32_t*>(p + kWideSeedVote), reinterpret_cast<Cand*>(p + kWideSeedSeed),
+                      reinterpret_cast<Cand*>(p + kWideSeedSamp), reinterpret_cast<float*>(p + kWideSeedSapx)};
 }
 
-struct WsLists {
-    Cand* c;        // candidate lists
-    uint32_t* ctr;  // arrival counters (header)
-};
-static inline WsLists carve(void* ws, int64_t nlists, int q) {
-    (void)nlists;
-    (void)q;
-    uintptr_t p = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
-    WsLists w;
-    w.ctr = reinterpret_cast<uint32_t*>(p);
-    w.c = reinterpret_cast<Cand*>(p + kWsHeader);
-    return w;
+// Every selection entry point starts here: ce_last_kernel() reads "" unless
+// this call notes a kernel.
+static inline hipStream_t enter(ce_stream_t stream) {
+    note_kernel("%s", "");
+    return (hipStream_t)stream;
 }
 
 // Any q >= 0, as the reference's -q (amg_test.py:547-553): argsort[::-1][:q]
@@ -262,17 +253,21 @@ CE_HIDDEN bool launch_stream(const CommArgs& a, int G, int q, int64_t base_idx, 
                              const uint32_t* excl = nullptr);
 // The same with stage 2 folded in: the grid's last block merges the block
 // lists into the final (oval, oidx), or into q records at ocand (one launch
-// for the whole selection).  Returns 0 (no streaming kernel applies), 1
-// (launched WITHOUT the fold: the lists are in w, run a finish) or 2 (folded).
+// for the whole selection).
+enum class Stage1 {
+    kNone = 0,    // no streaming kernel applies: nothing launched
+    kLists = 1,   // launched WITHOUT the fold: the lists are in w, run a finish
+    kFolded = 2,  // launched, outputs written
+};
 struct FoldOut {
     double* oval;
     int64_t* oidx;
     Cand* ocand;
     const Cand* extra;  // one more list to merge (a chunked job's running list), or nullptr
-    void* wide_ws;      // kWideSeedBytes of workspace for the wide stream's floor + grid vote, or nullptr
+    void* wide_ws;      // the layout's seed region for the wide stream's floor + grid vote, or nullptr
 };
-CE_HIDDEN int launch_stream_fold(const CommArgs& a, int G, int q, int64_t base_idx, WsLists w, hipStream_t st,
-                                 const uint32_t* excl, FoldOut out);
+CE_HIDDEN Stage1 launch_stream_fold(const CommArgs& a, int G, int q, int64_t base_idx, WsLists w, hipStream_t st,
+                                    const uint32_t* excl, FoldOut out);
 // ce_launch_partial.hip: block-synchronous stage 1 (any q): committee,
 // precomputed entropies, an hc table.
 CE_HIDDEN int committee_partial(const CommArgs& a, const Seg& sg, int grid, int q, WsLists w, double* oval,
@@ -305,11 +300,7 @@ CE_HIDDEN bool launch_seg(const CommArgs& a, const int64_t* offsets, int64_t n, 
                           int bpu, int threads, double* oval, int64_t* oidx, Cand* wc, const uint32_t* excl,
                           hipStream_t st);
 
-// ce_launch_sort.hip: the sort path for q > CE_MAX_Q (ce_sort.hpp).  Workspace:
-// the 64 KiB header, then n entropies, two n-record buffers, the digit counts
-// and `extra_cands` records.
-CE_HIDDEN size_t sort_ws_bytes(int64_t n, int64_t extra_cands = 0);
-CE_HIDDEN SortWs sort_carve(void* ws, int64_t n, int64_t extra_cands = 0);
+// ce_launch_sort.hip: the sort path for q > CE_MAX_Q (ce_sort.hpp; its workspace: ws_sort, ce_ws.hpp).
 // records {order key (0 if excluded), idx0 + i} of ent[0..n) into out
 CE_HIDDEN void sort_keys(const double* ent, int64_t n, int64_t idx0, const uint32_t* excl, Cand* out, hipStream_t st);
 CE_HIDDEN void sort_keys_users(const double* ent, int64_t n, const int64_t* offsets, int U, Cand* out, hipStream_t st);
@@ -344,8 +335,29 @@ static inline void sort_select(const SortWs& s, const double* ent, int64_t n, in
     sort_out(sort_run(s, 0, st), n, q, oval, oidx, ocand, st);
 }
 
-static inline int finish_lists(WsLists w, int segments, int nl, int q, double* val_out, int64_t* idx_out,
-                               hipStream_t st) {
-    launch_finish_lists(w.c, segments, nl, q, val_out, idx_out, st);
-    return CE_OK;
+// q > CE_MAX_Q: the entropies of committee `a` (and then of `t`, the mix's hc
+// rows) into the sort workspace, viewed in s
+static inline int sort_entropies(const WsLayout& L, void* ws, const CommArgs& a, const CommArgs* t, SortWs& s,
+                                 hipStream_t st) {
+    int rc = check_sort_n(L.g.n);
+    if (rc) return rc;
+    s = sort_view(L, ws);
+    rc = launch_entropy(a, nullptr, s.ent, st);
+    if (!rc && t) rc = launch_entropy(*t, nullptr, s.ent + a.N, st);
+    return rc;
+}
+
+// an entropy vector -> the top q: the block lists + a merge, or the sort path
+// (the caller has run check_sort_n for q > CE_MAX_Q)
+static inline void select_entropies(const WsLayout& L, void* ws, const double* ent, int64_t N, int q, int64_t base_idx,
+                                    double* oval, int64_t* oidx, hipStream_t st) {
+    if (q > CE_MAX_Q) {
+        sort_select(sort_view(L, ws), ent, N, base_idx, nullptr, q, oval, oidx, nullptr, st);
+        return;
+    }
+    const int G = pool_blocks(N);
+    const WsLists w = lists_view(L, ws);
+    Seg sg{nullptr, N, G, base_idx};
+    partial_entropies(ent, sg, G, q, w, oval, oidx, G == 1, st);
+    if (G > 1) launch_finish_lists(w.c, 1, G, q, oval, oidx, st);
 }

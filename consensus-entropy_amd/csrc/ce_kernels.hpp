@@ -30,14 +30,13 @@
 #include "ce_small.hpp"
 #include "ce_members.hpp"
 #include "ce_abi.hpp"
+#include "ce_ws.hpp"  // kMinItemsPerBlock, kMaxBlocks, kWideVoteSamples
 
 namespace ce {
 
 constexpr int kBS = 256;          // stage-1 block: 4 waves
 constexpr int kFinBS = 1024;      // stage-2 block: 16 waves
-constexpr int kMinItemsPerBlock = 64;
 constexpr int64_t kSmallPoolBytes = 256 * 1024;  // below this one block does the whole selection
-constexpr int kMaxBlocks = 1024;  // stage-1 blocks per pool (4 per CU on 256 CUs)
 constexpr int kSegWaves = 16;     // waves per single-block pool / per user (k_stream_seg)
 
 // ---------------------------------------------------------------------------
@@ -370,7 +369,6 @@ __global__ __launch_bounds__(kBS) void k_stream_wide(WideArgs a, PwPlan pl, Stre
 // any pool above it whatever the pool's order (a rising-entropy pool included),
 // so single selections and first chunks get the deep grid too.  The samples
 // read 1/16 of a small launch's items and 256 MB of a 128 GB C5 chunk.
-constexpr int kWideVoteSamples = 4096;
 constexpr int kWideVoteDen = 16;
 // samples of an N-item launch: N / 16, at most kWideVoteSamples (the launcher
 // runs the path from 1024 samples on: N >= 16384)

@@ -244,44 +244,6 @@ __global__ __launch_bounds__(256) void k_fill_pad(int64_t q, double* __restrict_
 
 }  // namespace ce
 
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-static SortGeom sort_geom(int64_t n) {
-    SortGeom g;
-    g.n = n;
-    int64_t chunk = cdiv(n < 1 ? 1 : n, (int64_t)kSortMaxWaves);
-    if (chunk < kSortMinChunk) chunk = kSortMinChunk;
-    g.chunk = (chunk + 63) / 64 * 64;
-    g.nw = (int)cdiv(n < 1 ? 1 : n, g.chunk);
-    return g;
-}
-
-size_t sort_ws_bytes(int64_t n, int64_t extra_cands) {
-    if (n < 0) n = 0;
-    const SortGeom g = sort_geom(n);
-    return kWsHeader + 256 + al256((size_t)n * 8) + 2 * al256((size_t)n * 16) + al256((size_t)256 * g.nw * 4) +
-           al256(256 * 8) + al256((size_t)(extra_cands > 0 ? extra_cands : 0) * 16);
-}
-
-SortWs sort_carve(void* ws, int64_t n, int64_t extra_cands) {
-    (void)extra_cands;
-    SortWs s;
-    s.g = sort_geom(n);
-    uintptr_t p = (((uintptr_t)ws + 255) & ~(uintptr_t)255) + kWsHeader;
-    s.ent = reinterpret_cast<double*>(p);
-    p += al256((size_t)n * 8);
-    s.a = reinterpret_cast<Cand*>(p);
-    p += al256((size_t)n * 16);
-    s.b = reinterpret_cast<Cand*>(p);
-    p += al256((size_t)n * 16);
-    s.hist = reinterpret_cast<uint32_t*>(p);
-    p += al256((size_t)256 * s.g.nw * 4);
-    s.dtot = reinterpret_cast<uint64_t*>(p);
-    p += al256(256 * 8);
-    s.extra = reinterpret_cast<Cand*>(p);
-    return s;
-}
-
 static inline int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), 8192)); }
 
 void sort_keys(const double* ent, int64_t n, int64_t idx0, const uint32_t* excl, Cand* out, hipStream_t st) {

@@ -35,9 +35,9 @@ bool launch_stream(const CommArgs& a, int G, int q, int64_t base_idx, WsLists w,
     return launch_stream_impl(a, G, q, base_idx, w, st, excl, nullptr) != 0;
 }
 
-int launch_stream_fold(const CommArgs& a, int G, int q, int64_t base_idx, WsLists w, hipStream_t st,
-                       const uint32_t* excl, FoldOut out) {
-    return launch_stream_impl(a, G, q, base_idx, w, st, excl, &out);
+Stage1 launch_stream_fold(const CommArgs& a, int G, int q, int64_t base_idx, WsLists w, hipStream_t st,
+                          const uint32_t* excl, FoldOut out) {
+    return static_cast<Stage1>(launch_stream_impl(a, G, q, base_idx, w, st, excl, &out));
 }
 
 static int launch_stream_impl(const CommArgs& a, int G, int q, int64_t base_idx, WsLists w, hipStream_t st,

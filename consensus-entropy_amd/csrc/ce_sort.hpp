@@ -26,11 +26,9 @@
 // maps to: they sort last and read back as padding.
 #pragma once
 #include "ce_topq.hpp"
+#include "ce_ws.hpp"  // SortGeom, kSortMaxWaves, kSortMinChunk, the layout (ws_sort)
 
 namespace ce {
-
-constexpr int kSortMaxWaves = 4096;
-constexpr int64_t kSortMinChunk = 1024;  // items per wave at least (16 steps)
 
 // One pass: digit of a record.  field 0: the key, descending; field 1: the
 // position bits [shift, shift + 8), ascending.
@@ -39,19 +37,13 @@ struct SortPass {
     int shift;
 };
 
-struct SortGeom {
-    int64_t n;      // records
-    int64_t chunk;  // records per wave (a multiple of 64)
-    int nw;         // waves (= cdiv(n, chunk))
-};
-
 // Batched users on the sort path: the record's position holds (user <<
 // kUserShift) | user-local position
 constexpr int kUserShift = 40;
 constexpr int kSortMaxUsers = 1 << 23;
 
-// The sort path's workspace (after the 64 KiB header): entropies, two record
-// buffers, the per-wave digit counts, the digit totals, and `extra` records.
+// The sort path's workspace, typed (sort_view of a ws_sort layout): entropies,
+// two record buffers, the per-wave digit counts, the digit totals, `extra` records.
 struct SortWs {
     double* ent;
     Cand* a;

@@ -20,6 +20,7 @@
 #pragma once
 #include "ce_device.hpp"
 #include "ce_topq.hpp"
+#include "ce_ws.hpp"
 
 namespace ce {
 
@@ -357,7 +358,7 @@ struct ItemTile {
     }
 };
 
-constexpr int kStreamMaxQ = 64;  // one list slot per lane
+// kStreamMaxQ (64: one list slot per lane): ce_ws.hpp
 
 // block-merge scratch: the wave lists, 64 slots each
 template <int WAVES>
