@@ -1,5 +1,5 @@
 // ce_abi.hpp -- error reporting shared by the translation units of libce_amd.so
-// (ce_kernels.hip defines them; ce_xgb.hip uses them).  Hidden: not part of
+// (ce_abi_core.hip defines them; every other one uses them).  Hidden: not part of
 // the exported C-ABI.
 #pragma once
 #define CE_HIDDEN __attribute__((visibility("hidden")))

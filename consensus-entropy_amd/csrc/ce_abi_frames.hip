@@ -1,8 +1,7 @@
 // ce_abi_frames.hip -- C-ABI (include/ce.h): frames -> committee entropy ->
 // top-q in one pass (k_frames_select, ce_frames.hpp).
+#include "ce_dispatch.hpp"  // resident_grid
 #include "ce_frames.hpp"
-#include "ce_abi.hpp"
-#include "ce_host.hpp"
 
 using namespace ce;
 

@@ -18,7 +18,9 @@
 // perm[off[n]] .. perm[off[n+1]-1] (perm == nullptr: off[n] .. off[n+1]-1),
 // songs in sorted s_id order as groupby returns them.
 #pragma once
-#include "ce_stream.hpp"
+#include "ce_merge.hpp"  // fold_merge
+#include "ce_wave.hpp"
+#include "ce_ws.hpp"  // kStreamMaxQ
 
 namespace ce {
 

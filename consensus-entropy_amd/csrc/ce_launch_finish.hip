@@ -3,6 +3,7 @@
 // The only TU that instantiates k_merge_reg / k_finish_heads / k_finish /
 // k_merge_wave.
 #include "ce_host.hpp"
+#include "ce_merge.hpp"
 
 using namespace ce;
 

@@ -1,24 +1,31 @@
 // ce_launch_partial.hip -- block-synchronous stage 1 (k_partial /
 // k_partial_wide: any q, per-block LDS top-q) for committees, precomputed
 // entropy vectors and hc tables.  The only TU that instantiates them.
-#include "ce_host.hpp"
+#include "ce_dispatch.hpp"
+#include "ce_partial.hpp"
 
 using namespace ce;
+
+// f(cap, final) with compile-time values: the block's LDS buffer (1024 slots for
+// q <= 256, else 4096) and whether the block writes the final (val, idx)
+template <class F>
+static inline void with_cap_final(int q, bool final_out, F&& f) {
+    if (q <= 256) {
+        if (final_out) f(std::integral_constant<int, 1024>(), std::true_type());
+        else f(std::integral_constant<int, 1024>(), std::false_type());
+    } else {
+        if (final_out) f(std::integral_constant<int, 4096>(), std::true_type());
+        else f(std::integral_constant<int, 4096>(), std::false_type());
+    }
+}
 
 template <class Src>
 static void launch_partial(const Src& src, const Seg& sg, int grid, int q, WsLists w, double* oval,
                            int64_t* oidx, bool final_out, hipStream_t st) {
-    if (q <= 256) {
-        if (final_out)
-            hipLaunchKernelGGL((k_partial<Src, 1024, true>), dim3(grid), dim3(kBS), 0, st, src, sg, q, w.c, oval, oidx);
-        else
-            hipLaunchKernelGGL((k_partial<Src, 1024, false>), dim3(grid), dim3(kBS), 0, st, src, sg, q, w.c, oval, oidx);
-    } else {
-        if (final_out)
-            hipLaunchKernelGGL((k_partial<Src, 4096, true>), dim3(grid), dim3(kBS), 0, st, src, sg, q, w.c, oval, oidx);
-        else
-            hipLaunchKernelGGL((k_partial<Src, 4096, false>), dim3(grid), dim3(kBS), 0, st, src, sg, q, w.c, oval, oidx);
-    }
+    with_cap_final(q, final_out, [&](auto cap, auto fin) {
+        hipLaunchKernelGGL((k_partial<Src, decltype(cap)::value, decltype(fin)::value>), dim3(grid), dim3(kBS), 0, st,
+                           src, sg, q, w.c, oval, oidx);
+    });
 }
 
 static void launch_partial_wide(const CommArgs& a, const Seg& sg, int grid, int q, WsLists w, double* oval,
@@ -29,21 +36,10 @@ static void launch_partial_wide(const CommArgs& a, const Seg& sg, int grid, int 
     with_wide_v(a, [&](auto dt, auto npl, auto vec) {
         constexpr int DT = decltype(dt)::value, NPL = decltype(npl)::value;
         constexpr bool VEC = decltype(vec)::value;
-        if (q <= 256) {
-            if (fin)
-                hipLaunchKernelGGL((k_partial_wide<DT, NPL, VEC, 1024, true>), dim3(grid), dim3(kBS), lds, st, wa, pl,
-                                   sg, q, w.c, oval, oidx);
-            else
-                hipLaunchKernelGGL((k_partial_wide<DT, NPL, VEC, 1024, false>), dim3(grid), dim3(kBS), lds, st, wa,
-                                   pl, sg, q, w.c, oval, oidx);
-        } else {
-            if (fin)
-                hipLaunchKernelGGL((k_partial_wide<DT, NPL, VEC, 4096, true>), dim3(grid), dim3(kBS), lds, st, wa, pl,
-                                   sg, q, w.c, oval, oidx);
-            else
-                hipLaunchKernelGGL((k_partial_wide<DT, NPL, VEC, 4096, false>), dim3(grid), dim3(kBS), lds, st, wa,
-                                   pl, sg, q, w.c, oval, oidx);
-        }
+        with_cap_final(q, fin, [&](auto cap, auto final_out) {
+            hipLaunchKernelGGL((k_partial_wide<DT, NPL, VEC, decltype(cap)::value, decltype(final_out)::value>),
+                               dim3(grid), dim3(kBS), lds, st, wa, pl, sg, q, w.c, oval, oidx);
+        });
     });
 }
 

@@ -2,7 +2,9 @@
 // batched users, the two-segment mix (tiled, ce_small.hpp), and the
 // multi-block k_stream_seg path.  The only TU that instantiates
 // k_select_tiles / k_stream_seg.
-#include "ce_host.hpp"
+#include "ce_dispatch.hpp"
+#include "ce_small.hpp"
+#include "ce_stream.hpp"  // k_stream_seg
 
 using namespace ce;
 

@@ -1,6 +1,8 @@
 // ce_launch_sort.hip -- the sort path for q beyond the list kernels (ce_sort.hpp):
 // the only TU that instantiates its kernels.
 #include "ce_host.hpp"
+#include "ce_merge.hpp"  // ListSrc (the rank merge reads the same list sources)
+#include "ce_wave.hpp"   // excluded
 
 using namespace ce;
 

@@ -1,8 +1,42 @@
 // ce_launch_stream.hip -- the streaming stage-1 launcher (the only TU that
 // instantiates k_stream_nmc / k_stream_direct / k_stream_wide2 / k_stream_wide).
-#include "ce_host.hpp"
+#include "ce_dispatch.hpp"
+#include "ce_stream.hpp"
+#include "ce_wide_stream.hpp"
 
 using namespace ce;
+
+static inline StreamArgs stream_args(const CommArgs& a, int G, int64_t base_idx) {
+    StreamArgs s;
+    s.p = a.p;
+    s.N = a.N;
+    s.M = a.M;
+    s.sN = a.sN;
+    s.sM = a.sM;
+    s.sC = a.sC;
+    s.dM = (double)a.M;
+    s.invM = 1.0 / (double)a.M;
+    s.pow2 = (a.M & (a.M - 1)) == 0;
+    s.base_idx = base_idx;
+    s.nlists = G;
+    s.per_wave = 0;
+    s.excl = nullptr;
+    s.ctr = nullptr;
+    s.oval = nullptr;
+    s.oidx = nullptr;
+    s.ocand = nullptr;
+    s.extra = nullptr;
+    s.vote = nullptr;
+    s.vote_heavy = 0;
+    s.seed = nullptr;
+    return s;
+}
+
+// the grid actually launched (<= G workspace lists) and its per-wave share
+static inline void stream_grid(StreamArgs& s, int grid) {
+    const int64_t W = (int64_t)grid * 4;
+    s.per_wave = (cdiv(s.N, W) + 63) / 64 * 64;
+}
 
 // (UNR members x IPL items) loads in flight per lane for the direct paths:
 // small committees batch items, large ones batch members.
@@ -17,6 +51,14 @@ static inline void with_batching(int M, F&& f) {
     }
 }
 
+
+// f(u) with the compile-time member rows per batch: UNR where it divides M (unr
+// == UNR), else 1
+template <int UNR, class F>
+static inline void with_unr(int unr, F&& f) {
+    if (unr == UNR) f(std::integral_constant<int, UNR>());
+    else f(std::integral_constant<int, 1>());
+}
 
 static int launch_stream_impl(const CommArgs& a, int G, int q, int64_t base_idx, WsLists w, hipStream_t st,
                               const uint32_t* excl, const FoldOut* fold);
@@ -57,17 +99,22 @@ static int launch_stream_impl(const CommArgs& a, int G, int q, int64_t base_idx,
     const int eb = elem_bytes(a.dt);
     const int64_t R = (int64_t)a.M * a.C * eb;
     const bool dense_nmc = a.sC == 1 && a.sM == a.C && a.sN == (int64_t)a.M * a.C && (uintptr_t)a.p % 16 == 0;
-    if (dense_nmc && (R == 256 || R == 512)) {
-#define CE_S(DT_, C_, S_)                                                                                   \
-    if (a.dt == DT_ && a.C == C_ && R == 16 * S_) {                                                       \
-        constexpr int RING_ = S_ == 16 ? 2 : 1; /* two 16-KiB tiles per wave: one block per CU */          \
-        auto kern = k_stream_nmc<DT_, C_, S_, CE_NMC_AUX, false, RING_>;                                  \
+// One LDS-DMA launch: MATCH_ is the layout's own test, S_ the 16-B chunks per
+// item (item-major) or the members (member-major, MNC_), AUX_ the cache policy.
+#define CE_NMC(MATCH_, DT_, C_, S_, AUX_, MNC_)                                                             \
+    if (a.dt == DT_ && a.C == C_ && (MATCH_)) {                                                           \
+        /* two 16-KiB tiles per wave: one block per CU (as measured: 16 chunks / 16 members) */           \
+        constexpr int RING_ = S_ == 16 ? 2 : 1;                                                           \
+        auto kern = k_stream_nmc<DT_, C_, S_, AUX_, MNC_, RING_>;                                         \
         const int grid = resident_grid(kern, 0, G);                                                       \
-        note_kernel("ce::k_stream_nmc<%d, %d, %d, %d, false, %d>", DT_, C_, S_, CE_NMC_AUX, RING_);        \
+        note_kernel("ce::k_stream_nmc<%d, %d, %d, %d, %s, %d>", DT_, C_, S_, AUX_, MNC_ ? "true" : "false", \
+                    RING_);                                                                               \
         stream_grid(sa, grid);                                                                            \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, sa, q, w.c);                               \
         return folded;                                                                                    \
     }
+    if (dense_nmc && (R == 256 || R == 512)) {
+#define CE_S(DT_, C_, S_) CE_NMC(R == 16 * S_, DT_, C_, S_, CE_NMC_AUX, false)
         CE_S(kF32, 4, 16) CE_S(kF32, 4, 32) CE_S(kBF16, 4, 16) CE_S(kBF16, 4, 32) CE_S(kF64, 4, 32)
         CE_S(kF32, 8, 16) CE_S(kF32, 8, 32)
 #undef CE_S
@@ -77,20 +124,12 @@ static int launch_stream_impl(const CommArgs& a, int G, int q, int64_t base_idx,
     const bool dense_mnc = a.sC == 1 && a.sN == a.C && a.C * eb == 16 && (a.sM * eb) % 16 == 0 &&
                            (uintptr_t)a.p % 16 == 0 && a.M >= 4;
     if (dense_mnc) {
-#define CE_SM(DT_, C_, M_)                                                                              \
-    if (a.dt == DT_ && a.C == C_ && a.M == M_) {                                                       \
-        constexpr int RING_ = M_ == 16 ? 2 : 1; /* as measured: 16 members (16-KiB tiles) */          \
-        auto kern = k_stream_nmc<DT_, C_, M_, 2, true, RING_>;                                         \
-        const int grid = resident_grid(kern, 0, G);                                                    \
-        note_kernel("ce::k_stream_nmc<%d, %d, %d, 2, true, %d>", DT_, C_, M_, RING_);                   \
-        stream_grid(sa, grid);                                                                         \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, sa, q, w.c);                            \
-        return folded;                                                                                 \
-    }
+#define CE_SM(DT_, C_, M_) CE_NMC(a.M == M_, DT_, C_, M_, 2, true)
         CE_SM(kF32, 4, 4) CE_SM(kF32, 4, 8) CE_SM(kF32, 4, 16) CE_SM(kF32, 4, 20) CE_SM(kF32, 4, 32)
         CE_SM(kF64, 2, 8) CE_SM(kF64, 2, 16) CE_SM(kBF16, 8, 16)
 #undef CE_SM
     }
+#undef CE_NMC
     int rc = with_committee(a, [&](auto src) {
         using S = decltype(src);
         with_batching<S>(a.M, [&](auto unr, auto ipl) {
@@ -144,7 +183,7 @@ static int launch_stream_impl(const CommArgs& a, int G, int q, int64_t base_idx,
             // grid reads 0.86-0.89 (the same file).
             // heavy items in a launch that folds its lists (single selections, the
             // multi-GPU records, every chunk of a job): the sampled floor + grid
-            // vote (k_wide_seed / k_wide_seed_pick, ce_kernels.hpp), then both grids
+            // vote (k_wide_seed / k_wide_seed_pick, ce_wide_stream.hpp), then both grids
             bool voted = false;
             if constexpr (KCH <= 2)  // (wider lanes: 8 batches would spill)
                 voted = R >= kWideHeavyBytes && fold != nullptr && fold->wide_ws != nullptr &&
@@ -153,9 +192,10 @@ static int launch_stream_impl(const CommArgs& a, int G, int q, int64_t base_idx,
                 if constexpr (KCH <= 2) {
                     const WideSeedWs sw = wide_seed_carve(fold->wide_ws);
                     const int ns = (int)wide_nsamples(a.N);
-                    auto sk = unr == UNR ? k_wide_seed<DT, KCH, UNR> : k_wide_seed<DT, KCH, 1>;
-                    hipLaunchKernelGGL(sk, dim3((unsigned)cdiv(ns, 4)), dim3(256), lds, st, wa, pl, sa.base_idx, sa.excl,
-                                       sw.samp, sw.sapx);
+                    with_unr<UNR>(unr, [&](auto u) {
+                        hipLaunchKernelGGL((k_wide_seed<DT, KCH, decltype(u)::value>), dim3((unsigned)cdiv(ns, 4)),
+                                           dim3(256), lds, st, wa, pl, sa.base_idx, sa.excl, sw.samp, sw.sapx);
+                    });
                     hipLaunchKernelGGL(k_wide_seed_pick<kWideVoteSamples>, dim3(1), dim3(1024), 0, st, sw.samp, sw.sapx, ns, q,
                                        fold->extra, sw.seed, sw.vote);
                     StreamArgs sh = sa, so = sa;
@@ -163,21 +203,17 @@ static int launch_stream_impl(const CommArgs& a, int G, int q, int64_t base_idx,
                     sh.seed = so.seed = sw.seed;
                     sh.vote_heavy = 1;
                     so.vote_heavy = 0;
-                    if (unr == UNR) {
-                        go(k_stream_wide2<DT, KCH, UNR, 8>, 8, 1, sh);
-                        go(k_stream_wide2<DT, KCH, UNR, 2>, 2, 1 << 20, so);
-                    } else {
-                        go(k_stream_wide2<DT, KCH, 1, 8>, 8, 1, sh);
-                        go(k_stream_wide2<DT, KCH, 1, 2>, 2, 1 << 20, so);
-                    }
+                    with_unr<UNR>(unr, [&](auto u) {
+                        go(k_stream_wide2<DT, KCH, decltype(u)::value, 8>, 8, 1, sh);
+                        go(k_stream_wide2<DT, KCH, decltype(u)::value, 2>, 2, 1 << 20, so);
+                    });
                     note_kernel("ce::k_stream_wide2<%d, %d, %d, 8>|ce::k_stream_wide2<%d, %d, %d, 2>", DT, KCH, unr,
                                 DT, KCH, unr);
                 }
             } else {
                 // a 2-batch register ring at the occupancy grid (3 and 4 measured:
                 // 72.8 / 71.9 % vs 72.6 % at C5 in round 2)
-                if (unr == UNR) go(k_stream_wide2<DT, KCH, UNR, 2>, 2, 1 << 20, sa);
-                else go(k_stream_wide2<DT, KCH, 1, 2>, 2, 1 << 20, sa);
+                with_unr<UNR>(unr, [&](auto u) { go(k_stream_wide2<DT, KCH, decltype(u)::value, 2>, 2, 1 << 20, sa); });
             }
         } else {  // strided / unaligned rows: the unpipelined wave-per-item kernel
             if (sa.excl) {  // k_stream_wide takes no bitmap

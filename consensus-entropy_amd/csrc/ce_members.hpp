@@ -27,7 +27,7 @@
 #pragma once
 #include "ce_device.hpp"
 #include "ce_glibc_exp.hpp"
-#include "ce_stream.hpp"
+#include "ce_wave.hpp"
 #include "ce_wide.hpp"
 
 namespace ce {

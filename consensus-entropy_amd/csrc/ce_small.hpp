@@ -38,7 +38,9 @@
 // than 64*W survivors (floods of near-ties at the floor), takes per-wave
 // register lists + a tree merge instead (block-uniform branches, same answer).
 #pragma once
-#include "ce_stream.hpp"
+#include "ce_src.hpp"     // kSmallThrottle, NoHook
+#include "ce_stream.hpp"  // stream_direct_range
+#include "ce_wave.hpp"
 
 namespace ce {
 

@@ -12,15 +12,31 @@
 //     (best first), cut to q entries and the threshold is raised.
 // The total order is (key desc, index asc) -- keys+indices are unique, so the
 // sort is a strict order and the result is deterministic.
+//
+// Also here, because the entry points pass them without seeing a kernel: the
+// candidate record (Cand), the stage-1 block size (kBS) and the segment
+// geometry of the block-synchronous stage 1 (Seg); and write_list, the engine's
+// output step.  No kernel in this header.
 #pragma once
 #include "ce_device.hpp"
 
 namespace ce {
 
+constexpr int kBS = 256;          // stage-1 block: 4 waves
+
 // One workspace candidate: order key + position, one 16-B load/store.
 struct __attribute__((aligned(16))) Cand {
     uint64_t key;
     int64_t idx;
+};
+
+// Segment geometry: block b -> segment b / bpu, chunk b % bpu.
+struct Seg {
+    const int64_t* offsets;  // [U+1] device, or nullptr: one segment [0, N)
+    int64_t N;
+    int bpu;
+    int64_t base_idx;
+    const uint32_t* excl;    // exclusion bitmap over items 0..N-1 (one segment), or nullptr
 };
 
 template <int CAP>
@@ -138,5 +154,21 @@ struct TopQ {
         return n < q ? n : q;
     }
 };
+
+// Write a finished top-q: either (key, idx) candidates into the workspace, or
+// the final (val, idx) outputs.  Slots past `cnt` are padding (idx -1).
+template <int CAP, bool FINAL>
+__device__ __forceinline__ void write_list(const TopQSmem<CAP>& s, int cnt, int q, Cand* wc, double* oval,
+                                           int64_t* oidx) {
+    for (int r = threadIdx.x; r < q; r += blockDim.x) {
+        const bool ok = r < cnt;
+        if constexpr (FINAL) {
+            oval[r] = ok ? key_to_val(s.key[r]) : __longlong_as_double(0x7ff8000000000000ll);
+            oidx[r] = ok ? s.idx[r] : -1;
+        } else {
+            wc[r] = Cand{ok ? s.key[r] : 0ull, ok ? s.idx[r] : -1};
+        }
+    }
+}
 
 }  // namespace ce

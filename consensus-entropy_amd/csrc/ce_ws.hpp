@@ -27,7 +27,7 @@ namespace ce {
 constexpr int kMinItemsPerBlock = 64;
 constexpr int kMaxBlocks = 1024;        // stage-1 blocks per pool (4 per CU on 256 CUs)
 constexpr int kStreamMaxQ = 64;         // the streaming kernels' q: one list slot per lane
-constexpr int kWideVoteSamples = 4096;  // the wide stream's floor samples (ce_kernels.hpp)
+constexpr int kWideVoteSamples = 4096;  // the wide stream's floor samples (ce_wide_stream.hpp)
 constexpr size_t kCandBytes = 16;       // one candidate record (Cand, ce_topq.hpp)
 constexpr int kSortMaxWaves = 4096;
 constexpr int64_t kSortMinChunk = 1024;  // items per wave at least (16 steps)

@@ -1,6 +1,6 @@
 """Per-kernel resources (VGPRs, AGPRs, scratch, static LDS) read from a built
 object's gfx950 code object -- no recompilation.
-  python tools/kernel_meta.py consensus-entropy_amd/build/ce_kernels.o [name-filter]"""
+  python tools/kernel_meta.py consensus-entropy_amd/build/ce_launch_stream.o [name-filter]"""
 import os
 import re
 import subprocess
