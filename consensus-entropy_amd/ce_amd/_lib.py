@@ -89,6 +89,15 @@ class CEError(RuntimeError):
         self.code = code
 
 
+class CEInvalidError(CEError, ValueError):
+    """CE_EINVAL (a bad argument): a ValueError, as before, and a CEError like
+    every other refusal of the engine, so `except CEError` sees them all."""
+
+    def __init__(self, fn, code, msg):
+        ValueError.__init__(self, f"{fn}: {msg}")
+        self.code = code
+
+
 def source_hash(pkg_dir=_PKG):
     """The content hash of the engine's sources in this tree, by the Makefile's
     rule (SRC_HASH): sha256 over the sorted csrc/*.hip, csrc/*.hpp files, then
@@ -190,6 +199,6 @@ def call(name, *args):
     if rc != CE_OK:
         msg = lib.ce_last_error().decode(errors="replace")
         if rc == CE_EINVAL:
-            raise ValueError(f"{name}: {msg}")
+            raise CEInvalidError(name, rc, msg)
         raise CEError(name, rc, msg)
     return rc

@@ -48,8 +48,12 @@ extern "C" int ce_select_mix(const void* p, ce_dtype dt, int64_t N, int32_t M, i
     const WsLists w2{ws_ptr<Cand>(ws, L.seg2), w.ctr};
     if (!launch_stream(t, G2, q, N, w2, st)) {
         Seg s2{nullptr, N_h, G2, N};
-        if (partial_table(hc, ld_hc, C, s2, G2, q, w2, st) != CE_OK)
-            return fail(CE_EUNSUPPORTED, "mix with C=%d has no kernel in this build", C);
+        // no TableSrc<C> (C outside {2, 3, 4, 8}): the table as the one-member
+        // committee it already is for q <= 64 and for the sort path -- the wide
+        // kernels, same list layout
+        rc = partial_table(hc, ld_hc, C, s2, G2, q, w2, st);
+        if (rc == CE_EUNSUPPORTED) rc = committee_partial(t, s2, G2, q, w2, nullptr, nullptr, false, st);
+        if (rc) return fail(CE_EUNSUPPORTED, "mix with C=%d has no kernel in this build", C);
     }
     launch_finish_lists(w.c, 1, G1 + G2, q, val_out, idx_out, st);  // lists + seg2: one array of G1 + G2 lists
     return check_launch("ce_select_mix");

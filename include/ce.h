@@ -91,7 +91,8 @@ int ce_committee_entropy(const void *p, ce_dtype dt, int64_t N, int32_t M, int32
  *   other value e.g. -1 is missing), freq = np.round(count / n_votes, 3),
  *   ent = scipy.stats.entropy(freq).  A row with no vote gives NaN.
  * votes: [N, A] int8 with row stride ld (bytes).  freq_or_null: [N, C] f64 out.
- * C in [1, 8].
+ * C in [1, 8].  N = 0 does nothing; A = 0 reads no vote (every row NaN), so
+ * votes may be NULL there.
  */
 int ce_vote_entropy(const int8_t *votes, int64_t N, int32_t A, int32_t C, int64_t ld,
                     double *freq_or_null, double *ent, ce_stream_t stream);
