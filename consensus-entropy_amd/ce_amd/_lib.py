@@ -77,6 +77,12 @@ SIGNATURES = {
     "ce_select_batched_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "ce_select_batched": (_int, [_vp, _int, _i64, _i32, _i32, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _sz, _vp,
                                  _vp, _vp]),
+    "ce_select_batched_excl": (_int, [_vp, _int, _i64, _i32, _i32, _i64, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _sz,
+                                      _vp, _vp, _vp]),
+    "ce_select_batched_mix_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "ce_select_batched_mix": (_int, [_vp, _int, _i64, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i32,
+                                     _vp, _vp, _i32, _vp, _sz, _vp, _vp, _vp]),
+    "ce_mark_selected_batched": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,203 @@
+"""Device-resident multi-epoch selection for U users at once.
+
+The reference's hot loop is users x epochs x mode (amg_test.py:345, :396-397,
+:425-489): every user has their own pool, and it shrinks every epoch
+(:455/:484 the hc frame, :521-531 X_train).  ``SelectionSession`` keeps ONE
+user's full pool on the device with an exclusion bitmap; a
+``BatchedSelectionSession`` does the same for all U users, epoch-major: each
+epoch is one selection launch over every user's remaining songs and one mark
+launch, instead of a Python loop of about five small launches per user.
+
+The users' pools are stacked: user u owns items ``offsets[u]:offsets[u+1]`` of
+the committee tensor (and rows ``hc_offsets[u]:hc_offsets[u+1]`` of the stacked
+hc tables).  The bitmaps are over the stacked (global) indices.  Positions
+returned are positions in each user's FULL pool, stable across epochs, with
+the conventions of ``SelectionSession``: in mix mode i in [0, N_u) is committee
+item i and N_u + j is row j of the user's table, which keeps its own row order.
+
+Modes:
+  mc    one ``ops.select_batched(excl=)`` and one mark per epoch
+  hc    the same over the stacked tables as a one-member f64 committee
+  mix   one ``ops.select_batched_mix`` and one mark.  ``hc_to_mc`` is a flat
+        [total_h] array: per hc row, the user-local committee item of the same
+        song, or -1 (the song is not in that user's committee pool).  A pick
+        through either part removes the song from both (:484 + :521-531).
+        The engine runs the mix in one launch for C = 4 and q <= 64; any other
+        shape is composed from two ``select_batched(excl=)`` calls and a
+        per-user ``ops.topq_merge`` -- the same picks, many more launches.
+  rand  not offered: the reference draws user by user from ONE global MT19937
+        stream (np.random.seed(1987), :55; the user loop, :345), so user u's
+        epoch-e draw comes after ALL of user u-1's epochs.  An epoch-major
+        batch cannot reproduce that order of draws; run one
+        ``SelectionSession("rand")`` per user, user-major, as the reference does.
+
+``select`` reads the picks back (one [U, q] copy per epoch).  ``step`` is the
+device half alone -- select + mark, nothing synchronised, capturable in a HIP
+graph -- and ``account`` the host half for picks read back later.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import ops
+from .select import MODES, _device, _hc_tensor, stack_committee
+
+_MIX_KERNEL_MAX_Q = 64  # include/ce.h: ce_select_batched_mix runs C = 4, q <= 64
+
+
+def _offsets_host(offsets, what):
+    o = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64).reshape(-1)
+    if o.shape[0] < 2 or o[0] < 0 or (np.diff(o) < 0).any():
+        raise ValueError(f"{what} must hold U + 1 >= 2 non-decreasing entries >= 0")
+    return o
+
+
+class BatchedSelectionSession:
+    def __init__(self, queries, mode, offsets, *, hc=None, hc_offsets=None, hc_to_mc=None, device=None):
+        if mode not in MODES:
+            raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+        if mode == "rand":
+            raise ValueError("BatchedSelectionSession has no rand mode: the reference draws user by user from one "
+                             "global RNG stream, which an epoch-major batch cannot reproduce; use one "
+                             "SelectionSession('rand') per user")
+        self.q = int(queries)
+        if self.q < 0:
+            raise ValueError(f"queries = {self.q} is negative")
+        self.mode = mode
+        # ---- host-side geometry and validation (before any device work)
+        off = _offsets_host(offsets, "offsets")
+        self.U = off.shape[0] - 1
+        off_h = None
+        if mode in ("hc", "mix"):
+            off_h = off if hc_offsets is None else _offsets_host(hc_offsets, "hc_offsets")
+            if off_h.shape[0] != off.shape[0]:
+                raise ValueError(f"hc_offsets must hold U + 1 = {self.U + 1} entries")
+            if hc is None:
+                raise ValueError("hc/mix modes need `hc`, the users' frequency tables stacked [total_h, C]")
+            if not hasattr(hc, "shape"):
+                hc = np.asarray(hc, dtype=np.float64)
+            if len(hc.shape) != 2 or hc.shape[0] != off_h[-1]:
+                raise ValueError(f"hc must be [total_h = {off_h[-1]}, C], the users' tables one after the other")
+        if mode == "hc":  # the pool IS the table
+            off = off_h
+        self._off, self._off_h = off, off_h
+        self.n_items = np.diff(off)
+        self.n_rows = np.diff(off_h) if mode == "mix" else None
+        h2m_g = m2h_g = None
+        if mode == "mix":
+            total_h = int(hc.shape[0])
+            if hc_to_mc is None:
+                if not np.array_equal(off_h, off):
+                    raise ValueError("mix: pass hc_to_mc (user-local committee item of each hc row) when "
+                                     "hc_offsets differ from offsets")
+                h2m = np.concatenate([np.arange(n) for n in self.n_items] + [np.zeros(0, np.int64)])
+            else:
+                h2m = np.asarray(hc_to_mc, dtype=np.int64).reshape(-1)
+            if h2m.shape[0] != total_h:
+                raise ValueError(f"hc_to_mc must hold one entry per hc row ({total_h})")
+            self._h2m_local = h2m
+            h2m_g = np.full(total_h, -1, np.int64)
+            m2h_g = np.full(int(off[-1]), -1, np.int64)
+            for u in range(self.U):
+                rows = np.arange(off_h[u], off_h[u + 1])
+                loc = h2m[rows]
+                if (loc >= self.n_items[u]).any() or (loc < -1).any():
+                    raise ValueError(f"hc_to_mc must give, per hc row, a committee item in [0, N_u) or -1 (user {u})")
+                ok = loc >= 0
+                if len(np.unique(loc[ok])) != ok.sum():
+                    raise ValueError(f"hc_to_mc maps two hc rows to one committee item (user {u})")
+                h2m_g[rows[ok]] = off[u] + loc[ok]
+                m2h_g[off[u] + loc[ok]] = rows[ok]
+        self.remaining = self.n_items.copy()
+        # ---- device state
+        self.dev = _device(device)
+        self.offsets = torch.from_numpy(off).to(self.dev)
+        self.excl = ops.excl_bitmap(int(off[-1]), self.dev)
+        self.H = self.hc_offsets = self.excl_h = self.h2m = self.m2h = None
+        if mode in ("hc", "mix"):
+            self.H = _hc_tensor(hc, None, None, self.dev).to(torch.float64).contiguous()
+        if mode == "mix":
+            self.hc_offsets = torch.from_numpy(off_h).to(self.dev)
+            self.excl_h = ops.excl_bitmap(self.H.shape[0], self.dev)
+            self.h2m = torch.from_numpy(h2m_g).to(self.dev)
+            self.m2h = torch.from_numpy(m2h_g).to(self.dev)
+            self._n_dev = torch.from_numpy(self.n_items).to(self.dev).unsqueeze(1)
+
+    def _slots(self):
+        """Output slots per user: q, but never more than the largest user's
+        pools hold, so a huge q costs no huge buffers."""
+        n = self.n_items + (self.n_rows if self.mode == "mix" else 0)
+        return int(min(self.q, n.max())) if self.U else 0
+
+    def _committee(self, committee, layout):
+        if committee is None:
+            raise ValueError(f"{self.mode} mode needs `committee`")
+        P, lay = stack_committee(committee, self.dev, layout)
+        n = P.shape[1] if lay == "MNC" else P.shape[0]
+        if n != self._off[-1]:
+            raise ValueError(f"committee covers {n} items, the users' pools hold {self._off[-1]}")
+        return P, lay
+
+    def step(self, committee=None, layout="MNC", *, _compose=False):
+        """One epoch on the device: selects every user's picks among their
+        remaining songs and marks them.  Returns idx [U, slots] (int64 device
+        tensor, -1 padding); nothing is synchronised and ``remaining`` is not
+        touched -- ``account`` does that once the picks are on the host."""
+        qs = self._slots()
+        if self.mode == "hc":
+            _, idx = ops.select_batched(self.H.unsqueeze(1), self.offsets, qs, "NMC", excl=self.excl)
+            ops.mark_selected_batched(idx, self.offsets, self.excl)
+            return idx
+        P, lay = self._committee(committee, layout)
+        if self.mode == "mc":
+            _, idx = ops.select_batched(P, self.offsets, qs, lay, excl=self.excl)
+            ops.mark_selected_batched(idx, self.offsets, self.excl)
+            return idx
+        C = P.shape[2]
+        if _compose or qs > _MIX_KERNEL_MAX_Q or C != 4:
+            idx = self._mix_composed(P, lay, qs)
+        else:
+            _, idx = ops.select_batched_mix(P, self.offsets, self.H, self.hc_offsets, qs, lay, excl=self.excl,
+                                            excl_h=self.excl_h)
+        ops.mark_selected_batched(idx, self.offsets, self.excl, self.hc_offsets, self.excl_h, self.m2h, self.h2m)
+        return idx
+
+    def _mix_composed(self, P, lay, qs):
+        """The mix epoch from the parts: each part's top-q per user, the hc
+        positions shifted by N_u, one merge per user (correct for any C and q;
+        U + 2 launches)."""
+        vm, im = ops.select_batched(P, self.offsets, qs, lay, excl=self.excl)
+        vh, ih = ops.select_batched(self.H.unsqueeze(1), self.hc_offsets, qs, "NMC", excl=self.excl_h)
+        ih = torch.where(ih >= 0, ih + self._n_dev, ih)
+        idx = torch.empty_like(im)
+        if qs:
+            for u in range(self.U):
+                _, idx[u] = ops.topq_merge(torch.cat([vm[u], vh[u]]), torch.cat([im[u], ih[u]]), qs)
+        return idx
+
+    def account(self, idx):
+        """The host half of an epoch: idx [U, slots] as ``step`` returned it ->
+        a list of U int64 arrays (each user's picks, best first) and the
+        ``remaining`` counts updated."""
+        rows = np.asarray(idx.cpu() if isinstance(idx, torch.Tensor) else idx, dtype=np.int64).reshape(self.U, -1)
+        out = []
+        for u in range(self.U):
+            r = rows[u][rows[u] >= 0]
+            out.append(r)
+            if self.mode == "mix":
+                # songs leaving the committee pool (an hc pick of a song outside it leaves only the table;
+                # a song picked through both parts in one epoch leaves once)
+                n = self.n_items[u]
+                via_hc = self._h2m_local[self._off_h[u] + r[r >= n] - n]
+                self.remaining[u] -= len(np.unique(np.concatenate([r[r < n], via_hc[via_hc >= 0]])))
+            else:
+                self.remaining[u] -= len(r)
+        return out
+
+    def select(self, committee=None, layout="MNC", *, _compose=False):
+        """One epoch: a list of U int64 arrays -- each user's picked positions
+        in their full pool, best first, fewer when a pool runs dry -- and the
+        picks leave the pools.  _compose (private, tests): force the composed
+        mix path."""
+        return self.account(self.step(committee, layout, _compose=_compose))

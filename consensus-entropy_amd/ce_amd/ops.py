@@ -806,19 +806,88 @@ def select_mix(P, hc, q, layout="MNC"):
     return vals, idx
 
 
-def select_batched(P, offsets, q, layout="MNC"):
+def _user_offsets(offsets, what="offsets", U=None):
+    _on_gpu(offsets, what)
+    offsets = offsets.to(torch.int64).contiguous()
+    if offsets.numel() < 2 or (U is not None and offsets.numel() != U + 1):
+        raise ValueError(f"{what} must hold U + 1 >= 2 entries" + (f" (U = {U})" if U is not None else ""))
+    return offsets
+
+
+def select_batched(P, offsets, q, layout="MNC", excl=None):
     """U users in one launch; user u owns items offsets[u]:offsets[u+1].
-    Returns (vals [U, q], idx [U, q]) with user-local positions."""
+    Returns (vals [U, q], idx [U, q]) with user-local positions.  excl: an
+    optional exclusion bitmap over the GLOBAL item index offsets[u] + i (int32
+    [ceil(N/32)], see excl_bitmap / mark_selected_batched): each user's
+    selection runs over the items whose bit is clear."""
     comm = _committee_args(P, layout)
     N = comm[2]
-    _on_gpu(offsets, "offsets")
-    offsets = offsets.to(torch.int64).contiguous()
+    offsets = _user_offsets(offsets)
     U = offsets.numel() - 1
-    if U < 1:
-        raise ValueError("offsets must hold U + 1 >= 2 entries")
     q = _check_q(q)
     lib = _lib.load()
     ws = WORKSPACE.get(P.device, lib.ce_select_batched_workspace_bytes(N, U, q), _sort_path(q))
     vals, idx = _outs(q, P.device, (U,))
-    call("ce_select_batched", *comm, _p(offsets), U, q, _p(ws), ws.numel(), _p(vals), _p(idx), _stream(P.device))
+    if excl is None:
+        call("ce_select_batched", *comm, _p(offsets), U, q, _p(ws), ws.numel(), _p(vals), _p(idx), _stream(P.device))
+    else:
+        _check_excl(excl, N)
+        call("ce_select_batched_excl", *comm, _p(offsets), U, _p(excl), q, _p(ws), ws.numel(), _p(vals), _p(idx),
+             _stream(P.device))
     return vals, idx
+
+
+def select_batched_mix(P, offsets, hc, hc_offsets, q, layout="MNC", excl=None, excl_h=None):
+    """amg_test.py:473-480 for U users in one launch: user u's row stack
+    [committee items offsets[u]:offsets[u+1]; rows hc_offsets[u]:hc_offsets[u+1]
+    of the stacked tables hc [total_h, C]].  Returns (vals [U, q], idx [U, q]),
+    user-local positions: i < N_u a committee item, N_u + j hc row j.  excl /
+    excl_h: optional bitmaps over the global item / hc row index.  The engine
+    runs C = 4, q <= 64 (CEError otherwise: BatchedSelectionSession composes)."""
+    comm = _committee_args(P, layout)
+    N, C = comm[2], comm[4]
+    _on_gpu(hc, "hc table")
+    if hc.dim() != 2 or hc.shape[1] != C:
+        raise ValueError(f"hc table must be [total_h, {C}]")
+    hc = hc.to(torch.float64)
+    if hc.stride(1) != 1:
+        hc = hc.contiguous()
+    offsets = _user_offsets(offsets)
+    U = offsets.numel() - 1
+    hc_offsets = _user_offsets(hc_offsets, "hc_offsets", U)
+    q = _check_q(q)
+    Nh = hc.shape[0]
+    if excl is not None:
+        _check_excl(excl, N)
+    if excl_h is not None:
+        _check_excl(excl_h, Nh)
+    lib = _lib.load()
+    ws = WORKSPACE.get(P.device, lib.ce_select_batched_mix_workspace_bytes(N, Nh, U, q), _sort_path(q))
+    vals, idx = _outs(q, P.device, (U,))
+    call("ce_select_batched_mix", *comm, _p(offsets), _p(hc), Nh, hc.stride(0), _p(hc_offsets), U, _p(excl),
+         _p(excl_h), q, _p(ws), ws.numel(), _p(vals), _p(idx), _stream(P.device))
+    return vals, idx
+
+
+def mark_selected_batched(idx, offsets, excl, hc_offsets=None, excl_h=None, m2h=None, h2m=None):
+    """Set the bits of a batched selection's picks idx [U, q] (user-local
+    positions, -1 ignored): a position below N_u marks global item offsets[u] +
+    p in excl (and hc row m2h[item] in excl_h), one above it hc row
+    hc_offsets[u] + p - N_u in excl_h (and item h2m[row] in excl).  The maps
+    hold global indices, -1 = no twin.  Stream-ordered, nothing leaves the GPU."""
+    _on_gpu(idx, "idx")
+    offsets = _user_offsets(offsets)
+    U = offsets.numel() - 1
+    if idx.dim() != 2 or idx.shape[0] != U:
+        raise ValueError(f"idx must be [U = {U}, q]")
+    idx = idx.to(torch.int64).contiguous()
+    _check_excl(excl, 0)
+    if hc_offsets is not None:
+        hc_offsets = _user_offsets(hc_offsets, "hc_offsets", U)
+    for name, t in (("excl_h", excl_h), ("m2h", m2h), ("h2m", h2m)):
+        if t is not None:
+            _on_gpu(t, name)
+            if t.dtype != (torch.int32 if name == "excl_h" else torch.int64) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {'int32 bitmap' if name == 'excl_h' else 'int64 map'}")
+    call("ce_mark_selected_batched", _p(idx), U, idx.shape[1], _p(offsets), _p(excl), _p(hc_offsets), _p(excl_h),
+         _p(m2h), _p(h2m), _stream(excl.device))

@@ -64,9 +64,12 @@ extern "C" size_t ce_select_batched_workspace_bytes(int64_t total_items, int32_t
     return ws_batched(total_items, U, q).bytes;
 }
 
-extern "C" int ce_select_batched(const void* p, ce_dtype dt, int64_t total_items, int32_t M, int32_t C, int64_t sN,
-                                 int64_t sM, int64_t sC, const int64_t* offsets, int32_t U, int32_t q, void* ws,
-                                 size_t ws_bytes, double* val_out, int64_t* idx_out, ce_stream_t stream) {
+// ce_select_batched and ce_select_batched_excl: one ladder (tiles, k_stream_seg,
+// committee_partial, sort), the bitmap handed down every rung (nullptr: none)
+static int select_batched(const char* fn, const void* p, ce_dtype dt, int64_t total_items, int32_t M, int32_t C,
+                          int64_t sN, int64_t sM, int64_t sC, const int64_t* offsets, int32_t U,
+                          const uint32_t* excl, int32_t q, void* ws, size_t ws_bytes, double* val_out,
+                          int64_t* idx_out, ce_stream_t stream) {
     const hipStream_t st = enter(stream);
     CommArgs a{p, (int)dt, total_items, M, C, sN, sM, sC};
     int rc = check_comm(a);
@@ -86,29 +89,76 @@ extern "C" int ce_select_batched(const void* p, ce_dtype dt, int64_t total_items
         SortWs s;
         rc = sort_entropies(L, ws, a, nullptr, s, st);
         if (rc) return rc;
-        sort_keys_users(s.ent, total_items, offsets, U, s.a, st);
+        sort_keys_users(s.ent, total_items, offsets, U, excl, s.a, st);
         sort_out_users(sort_run(s, user_sort_passes(U), st), offsets, U, q, val_out, idx_out, st);
-        return check_launch("ce_select_batched");
+        return check_launch(fn);
     }
     const int bpu = batched_bpu(total_items, U);
     const int64_t nl = (int64_t)bpu * U;
     const WsLists w = lists_view(L, ws);
     if (q <= kStreamMaxQ) {
         // one block per user (k_select_tiles; a user longer than its block streams inside it)
-        if (launch_small_users(a, offsets, U, q, val_out, idx_out, st)) return check_launch("ce_select_batched");
+        if (launch_small_users(a, offsets, U, q, val_out, idx_out, excl, st)) return check_launch(fn);
     }
     if (q <= kStreamMaxQ) {
         // bpu 4-wave blocks per user, then one wave per user merges its bpu lists
         if (launch_seg(a, offsets, 0, 0, q, (int)nl, bpu, bpu == 1 && U < 64 ? 64 * kSegWaves : 256, val_out, idx_out,
-                       w.c, nullptr, st)) {
+                       w.c, excl, st)) {
             if (bpu > 1) launch_merge_wave(w.c, U, bpu, q, val_out, idx_out, st);
-            return check_launch("ce_select_batched");
+            return check_launch(fn);
         }
     }
-    Seg sg{offsets, total_items, bpu, 0};
+    Seg sg{offsets, total_items, bpu, 0, excl};
     const bool fin = bpu == 1;
     rc = committee_partial(a, sg, (int)nl, q, w, val_out, idx_out, fin, st);
     if (rc) return dispatch_err(rc, a);
     if (!fin) launch_finish_lists(w.c, U, bpu, q, val_out, idx_out, st);
-    return check_launch("ce_select_batched");
+    return check_launch(fn);
+}
+
+extern "C" int ce_select_batched(const void* p, ce_dtype dt, int64_t total_items, int32_t M, int32_t C, int64_t sN,
+                                 int64_t sM, int64_t sC, const int64_t* offsets, int32_t U, int32_t q, void* ws,
+                                 size_t ws_bytes, double* val_out, int64_t* idx_out, ce_stream_t stream) {
+    return select_batched("ce_select_batched", p, dt, total_items, M, C, sN, sM, sC, offsets, U, nullptr, q, ws,
+                          ws_bytes, val_out, idx_out, stream);
+}
+
+extern "C" int ce_select_batched_excl(const void* p, ce_dtype dt, int64_t total_items, int32_t M, int32_t C,
+                                      int64_t sN, int64_t sM, int64_t sC, const int64_t* offsets, int32_t U,
+                                      const uint32_t* excl, int32_t q, void* ws, size_t ws_bytes, double* val_out,
+                                      int64_t* idx_out, ce_stream_t stream) {
+    return select_batched("ce_select_batched_excl", p, dt, total_items, M, C, sN, sM, sC, offsets, U, excl, q, ws,
+                          ws_bytes, val_out, idx_out, stream);
+}
+
+// ---- batched mix (ws_batched_mix, ce_ws.hpp) -----------------------------------
+extern "C" size_t ce_select_batched_mix_workspace_bytes(int64_t total_items, int64_t total_h, int32_t U, int32_t q) {
+    return ws_batched_mix(total_items, total_h, U, q).bytes;
+}
+
+extern "C" int ce_select_batched_mix(const void* p, ce_dtype dt, int64_t total_items, int32_t M, int32_t C, int64_t sN,
+                                     int64_t sM, int64_t sC, const int64_t* offsets, const double* hc, int64_t total_h,
+                                     int64_t ld_hc, const int64_t* offsets_h, int32_t U, const uint32_t* excl,
+                                     const uint32_t* excl_h, int32_t q, void* ws, size_t ws_bytes, double* val_out,
+                                     int64_t* idx_out, ce_stream_t stream) {
+    const hipStream_t st = enter(stream);
+    CommArgs a{p, (int)dt, total_items, M, C, sN, sM, sC};
+    int rc = check_comm(a);
+    if (rc) return rc;
+    rc = check_q(q);
+    if (rc) return rc;
+    if (U < 1 || !offsets || !offsets_h) return fail(CE_EINVAL, "bad batched arguments (U=%d, offsets, offsets_h)", U);
+    if (total_h < 0 || (total_h > 0 && (!hc || ld_hc < C)))
+        return fail(CE_EINVAL, "bad hc table (total_h=%lld, ld_hc=%lld < C=%d?)", (long long)total_h, (long long)ld_hc, C);
+    if (q > 0 && (!val_out || !idx_out)) return fail(CE_EINVAL, "null outputs");
+    if (q == 0) return CE_OK;
+    if (C != 4 || q > kStreamMaxQ)
+        return fail(CE_EUNSUPPORTED, "the batched mix runs C = 4 and q <= %d (got C=%d, q=%d): compose it from "
+                    "ce_select_batched_excl over either part and ce_topq_merge", kStreamMaxQ, C, q);
+    rc = check_ws(ws_batched_mix(total_items, total_h, U, q), ws, ws_bytes);
+    if (rc) return rc;
+    const CommArgs t{hc, kF64, total_h, 1, C, ld_hc, C, 1};  // the stacked tables: a one-member f64 committee
+    if (!launch_small_mix_users(a, t, offsets, offsets_h, U, q, val_out, idx_out, excl, excl_h, st))
+        return dispatch_err(CE_EUNSUPPORTED, a);
+    return check_launch("ce_select_batched_mix");
 }

@@ -156,9 +156,13 @@ CE_HIDDEN void launch_merge_wave(const Cand* c, int segs, int nl, int q, double*
 constexpr int64_t kSmallPoolItems = 4096;
 CE_HIDDEN bool launch_small_pool(const CommArgs& a, int64_t base_idx, int q, double* oval, int64_t* oidx,
                                  const uint32_t* excl, WsLists w, hipStream_t st);
-// U users (offsets[U+1]) in one launch, one block per user
+// U users (offsets[U+1]) in one launch, one block per user (excl: over the tensor's items, or nullptr)
 CE_HIDDEN bool launch_small_users(const CommArgs& a, const int64_t* offsets, int U, int q, double* oval,
-                                  int64_t* oidx, hipStream_t st);
+                                  int64_t* oidx, const uint32_t* excl, hipStream_t st);
+// the mix of U users in one launch (C = 4): user u's committee items offsets[u] .. and hc rows offsets_h[u] ..
+CE_HIDDEN bool launch_small_mix_users(const CommArgs& a, const CommArgs& t, const int64_t* offsets,
+                                      const int64_t* offsets_h, int U, int q, double* oval, int64_t* oidx,
+                                      const uint32_t* excl, const uint32_t* excl_h, hipStream_t st);
 // the mix of amg_test.py:473-480 ([mc; hc] rows, C = 4) in one launch
 CE_HIDDEN bool launch_small_mix(const CommArgs& a, const CommArgs& t, int q, double* oval, int64_t* oidx,
                                 hipStream_t st);
@@ -170,7 +174,8 @@ CE_HIDDEN bool launch_seg(const CommArgs& a, const int64_t* offsets, int64_t n, 
 // ce_launch_sort.hip: the sort path for q > CE_MAX_Q (ce_sort.hpp; its workspace: ws_sort, ce_ws.hpp).
 // records {order key (0 if excluded), idx0 + i} of ent[0..n) into out
 CE_HIDDEN void sort_keys(const double* ent, int64_t n, int64_t idx0, const uint32_t* excl, Cand* out, hipStream_t st);
-CE_HIDDEN void sort_keys_users(const double* ent, int64_t n, const int64_t* offsets, int U, Cand* out, hipStream_t st);
+CE_HIDDEN void sort_keys_users(const double* ent, int64_t n, const int64_t* offsets, int U, const uint32_t* excl,
+                               Cand* out, hipStream_t st);
 // sorts s.a[0..s.g.n) (generated in ascending position) by key descending, then
 // user_passes passes over the user bits; returns the buffer holding the result
 CE_HIDDEN const Cand* sort_run(const SortWs& s, int user_passes, hipStream_t st);

@@ -1,7 +1,7 @@
 // ce_launch_small.hip -- pools of a few thousand items: a single pool,
-// batched users, the two-segment mix (tiled, ce_small.hpp), and the
-// multi-block k_stream_seg path.  The only TU that instantiates
-// k_select_tiles / k_stream_seg.
+// batched users, the two-segment mix and the batched mix (tiled,
+// ce_small.hpp), and the multi-block k_stream_seg path.  The only TU that
+// instantiates k_select_tiles / k_select_tiles_mix / k_stream_seg.
 #include "ce_dispatch.hpp"
 #include "ce_small.hpp"
 #include "ce_stream.hpp"  // k_stream_seg
@@ -67,7 +67,7 @@ bool launch_small_pool(const CommArgs& a, int64_t base_idx, int q, double* oval,
 }
 
 bool launch_small_users(const CommArgs& a, const int64_t* offsets, int U, int q, double* oval, int64_t* oidx,
-                        hipStream_t st) {
+                        const uint32_t* excl, hipStream_t st) {
     if (U < 1) return false;
     bool launched = false;
     const int rc = with_committee(a, [&](auto src) {
@@ -77,7 +77,7 @@ bool launch_small_users(const CommArgs& a, const int64_t* offsets, int U, int q,
         // the average user must fit its block (a longer one streams inside it)
         if (cdiv(a.N, U) > (int64_t)512 * IPT) return;
         const TileArgs ta{offsets, 0, 0, 0};
-        launch_tiles<S, S, IPT, 0, 512, small_unr<S, 512>(), true>(src, src, ta, U, q, oval, oidx, nullptr, st);
+        launch_tiles<S, S, IPT, 0, 512, small_unr<S, 512>(), true>(src, src, ta, U, q, oval, oidx, excl, st);
         launched = true;
     });
     return rc == CE_OK && launched;
@@ -104,6 +104,35 @@ bool launch_small_mix(const CommArgs& a, const CommArgs& t, int q, double* oval,
             };
             if (vec_ok(t, CC)) go(make_src<kF64, CC, true>(t));
             else go(make_src<kF64, CC, false>(t));
+            launched = true;
+        }
+    });
+    return rc == CE_OK && launched;
+}
+
+// The mix for U users in one launch (k_select_tiles_mix): block u takes user
+// u's committee items and hc rows, in the geometry of the single mix above --
+// 1024 threads, 2 + 2 rows per thread, the table as a one-member f64 source.
+// A user longer than 2048 rows in either segment streams inside its block.
+bool launch_small_mix_users(const CommArgs& a, const CommArgs& t, const int64_t* offsets, const int64_t* offsets_h,
+                            int U, int q, double* oval, int64_t* oidx, const uint32_t* excl, const uint32_t* excl_h,
+                            hipStream_t st) {
+    if (U < 1 || a.C != 4) return false;
+    const MixTileArgs ta{offsets, offsets_h, excl, excl_h};
+    bool launched = false;
+    const int rc = with_committee(a, [&](auto src) {
+        using S = decltype(src);
+        if constexpr (S::kC == 4) {
+            constexpr int UNRA = S::kDT == kF64 ? 2 : 4;
+            auto go = [&](auto hsrc) {
+                using H = decltype(hsrc);
+                note_kernel("ce::k_select_tiles_mix<ce::CommitteeSrc<%d, %d, %s>, ce::CommitteeSrc<%d, %d, %s>, 2, 2, %d, 1, 1024>",
+                            S::kDT, S::kC, S::kVec ? "true" : "false", H::kDT, H::kC, H::kVec ? "true" : "false", UNRA);
+                hipLaunchKernelGGL((k_select_tiles_mix<S, H, 2, 2, UNRA, 1, 1024>), dim3((unsigned)U), dim3(1024), 0, st,
+                                   src, hsrc, ta, q, oval, oidx);
+            };
+            if (vec_ok(t, 4)) go(make_src<kF64, 4, true>(t));
+            else go(make_src<kF64, 4, false>(t));
             launched = true;
         }
     });

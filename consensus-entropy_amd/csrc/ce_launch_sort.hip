@@ -137,10 +137,11 @@ __global__ __launch_bounds__(256) void k_sort_keys(const double* __restrict__ en
 
 // Batched users: item g of user u (offsets[u] <= g < offsets[u+1]) ->
 // {order key, (u << kUserShift) | (g - offsets[u])}; items outside every user
-// get user U (sorted after all users).
+// get user U (sorted after all users).  Key 0 (after every entropy of its
+// user) for items whose exclusion bit is set (excl over items 0..n-1, or nullptr).
 __global__ __launch_bounds__(256) void k_sort_keys_users(const double* __restrict__ ent, int64_t n,
                                                           const int64_t* __restrict__ offsets, int U,
-                                                          Cand* __restrict__ out) {
+                                                          const uint32_t* __restrict__ excl, Cand* __restrict__ out) {
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
         int l = 0, h = U;  // the last u with offsets[u] <= g
         while (l < h) {
@@ -150,7 +151,9 @@ __global__ __launch_bounds__(256) void k_sort_keys_users(const double* __restric
         }
         const int64_t u = (g < offsets[0] || g >= offsets[U]) ? U : l;
         const int64_t local = u < U ? g - offsets[u] : 0;
-        out[g] = Cand{order_key(ent[g]), (int64_t)(((uint64_t)u << kUserShift) | (uint64_t)local)};
+        uint64_t k = order_key(ent[g]);
+        if (excl && excluded(excl, g)) k = 0ull;
+        out[g] = Cand{k, (int64_t)(((uint64_t)u << kUserShift) | (uint64_t)local)};
     }
 }
 
@@ -174,6 +177,7 @@ __global__ __launch_bounds__(256) void k_sort_out(const Cand* __restrict__ s, in
 
 // Batched users: user u's slots [u*q, (u+1)*q) from its contiguous run of the
 // sorted records (it starts at offsets[u] - offsets[0]); user-local positions.
+// Slots past the user's items or holding key 0 (excluded) are padding.
 __global__ __launch_bounds__(256) void k_sort_out_users(const Cand* __restrict__ s, const int64_t* __restrict__ offsets,
                                                          int U, int64_t q, double* __restrict__ oval,
                                                          int64_t* __restrict__ oidx) {
@@ -181,9 +185,10 @@ __global__ __launch_bounds__(256) void k_sort_out_users(const Cand* __restrict__
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
         const int64_t u = t / q, r = t - u * q;
         const int64_t len = offsets[u + 1] - offsets[u];
-        const bool ok = r < len;
-        CE_DASSERT(!ok || (offsets[u] >= offsets[0] && len >= 0));
-        const Cand c = ok ? s[offsets[u] - offsets[0] + r] : Cand{0ull, -1};
+        const bool in = r < len;
+        CE_DASSERT(!in || (offsets[u] >= offsets[0] && len >= 0));
+        const Cand c = in ? s[offsets[u] - offsets[0] + r] : Cand{0ull, -1};
+        const bool ok = in && c.key != 0ull;
         oval[t] = ok ? key_to_val(c.key) : __longlong_as_double(0x7ff8000000000000ll);
         oidx[t] = ok ? (int64_t)((uint64_t)c.idx & ((1ull << kUserShift) - 1ull)) : -1;
     }
@@ -252,8 +257,9 @@ void sort_keys(const double* ent, int64_t n, int64_t idx0, const uint32_t* excl,
     if (n > 0) hipLaunchKernelGGL(k_sort_keys, dim3(grid_for(n)), dim3(256), 0, st, ent, n, idx0, excl, out);
 }
 
-void sort_keys_users(const double* ent, int64_t n, const int64_t* offsets, int U, Cand* out, hipStream_t st) {
-    if (n > 0) hipLaunchKernelGGL(k_sort_keys_users, dim3(grid_for(n)), dim3(256), 0, st, ent, n, offsets, U, out);
+void sort_keys_users(const double* ent, int64_t n, const int64_t* offsets, int U, const uint32_t* excl, Cand* out,
+                     hipStream_t st) {
+    if (n > 0) hipLaunchKernelGGL(k_sort_keys_users, dim3(grid_for(n)), dim3(256), 0, st, ent, n, offsets, U, excl, out);
 }
 
 const Cand* sort_run(const SortWs& s, int user_passes, hipStream_t st) {

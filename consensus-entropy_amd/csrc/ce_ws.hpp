@@ -3,7 +3,7 @@
 // under ASan + UBSan and checks every layout over a grid of sizes).
 //
 // Every entry point computes ONE WsLayout from its size arguments (ws_topq,
-// ws_mc, ws_lists, ws_chunk, ws_mix, ws_batched, ws_frames).  Its `bytes` is
+// ws_mc, ws_lists, ws_chunk, ws_mix, ws_batched, ws_batched_mix, ws_frames).  Its `bytes` is
 // what the matching ce_*_workspace_bytes returns and what the entry point
 // checks the caller's workspace against; its regions are the only way to reach
 // workspace memory (ws_ptr, ce_host.hpp), as offsets from the 256-aligned base
@@ -206,6 +206,20 @@ static inline WsLayout ws_batched(int64_t total_items, int32_t U, int32_t q) {
     if (U < 1) U = 1;
     if (q > CE_MAX_Q) return ws_sort(total_items);
     return ws_list_layout((int64_t)batched_bpu(total_items, U) * U, q);
+}
+
+// ce_select_batched_mix: per user, the committee's lists (as ws_batched) and
+// then the hc rows' lists, one array of lists (it covers ws_batched of the
+// committee part, so one workspace serves both calls of a session)
+static inline WsLayout ws_batched_mix(int64_t total_items, int64_t total_h, int32_t U, int32_t q) {
+    if (U < 1) U = 1;
+    if (total_items < 0) total_items = 0;
+    if (total_h < 0) total_h = 0;
+    if (q > CE_MAX_Q) return ws_sort(total_items + total_h);
+    const int64_t nh = (int64_t)batched_bpu(total_h, U) * U;
+    WsLayout L = ws_list_layout((int64_t)batched_bpu(total_items, U) * U + nh, q);
+    L.seg2 = ws_split_lists(L, (size_t)nh * (size_t)L.q * kCandBytes);
+    return L;
 }
 
 // ce_select_frames: q <= 64 the streaming kernels' lists; 64 < q <= CE_MAX_Q

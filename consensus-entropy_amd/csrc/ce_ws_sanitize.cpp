@@ -110,9 +110,20 @@ int main() {
                 if (q <= CE_MAX_Q && L.seg2.bytes != (size_t)pool_blocks(Nh) * slot) die("ws_mix" + at, "seg2 bytes");
                 if (q <= CE_MAX_Q && L.bytes < ws_mc(N, q).bytes) die("ws_mix" + at, "does not cover ws_mc");
             }
-            for (int32_t U : Us)
-                check("ws_batched" + at + " U=" + std::to_string(U), ws_batched(N, U, q),
-                      (size_t)batched_bpu(N, U < 1 ? 1 : U) * (size_t)(U < 1 ? 1 : U) * slot);
+            for (int32_t U : Us) {
+                const size_t U1 = (size_t)(U < 1 ? 1 : U);
+                const size_t nu = (size_t)batched_bpu(N, (int)U1) * U1;
+                check("ws_batched" + at + " U=" + std::to_string(U), ws_batched(N, U, q), nu * slot);
+                for (int64_t Nh : Nhs) {  // the batched mix: total_h hc rows over the same users
+                    const std::string atm = at + " U=" + std::to_string(U) + " total_h=" + std::to_string(Nh);
+                    const size_t nh = (size_t)batched_bpu(Nh, (int)U1) * U1;
+                    const WsLayout L = ws_batched_mix(N, Nh, U, q);
+                    check("ws_batched_mix" + atm, L, (nu + nh) * slot);
+                    if (q <= CE_MAX_Q && L.seg2.bytes != nh * slot) die("ws_batched_mix" + atm, "seg2 bytes");
+                    if (L.bytes < ws_batched(N, U, q).bytes) die("ws_batched_mix" + atm, "does not cover ws_batched");
+                    if (q > CE_MAX_Q && L.g.n != (N > 0 ? N : 0) + Nh) die("ws_batched_mix" + atm, "sort records");
+                }
+            }
         }
     printf("ce_ws_sanitize: %ld layouts, %ld regions written: ok\n", g_layouts, g_touched);
     return 0;

@@ -371,6 +371,63 @@ int ce_select_batched(const void *p, ce_dtype dt, int64_t total_items, int32_t M
                       int32_t q, void *ws, size_t ws_bytes, double *val_out, int64_t *idx_out,
                       ce_stream_t stream);
 
+/*
+ * Batched multi-epoch selection -- the per-user loop (amg_test.py:345) around
+ * the epochs (:396-397) with each user's shrinking pool (:521-531) kept on the
+ * device: ce_select_batched over the items whose bit is clear.  excl is a
+ * bitmap over the GLOBAL item index offsets[u] + i (ce_excl_words(total_items)
+ * words, so words straddle users); NULL = ce_select_batched.  Output as
+ * ce_select_batched (user-local positions; -1 / NaN past a user's alive
+ * items); any q, the sort path's limits as there.  Workspace:
+ * ce_select_batched_workspace_bytes.
+ */
+int ce_select_batched_excl(const void *p, ce_dtype dt, int64_t total_items, int32_t M, int32_t C,
+                           int64_t sN, int64_t sM, int64_t sC, const int64_t *offsets, int32_t U,
+                           const uint32_t *excl, int32_t q, void *ws, size_t ws_bytes, double *val_out,
+                           int64_t *idx_out, ce_stream_t stream);
+
+/*
+ * Batched mix -- replaces amg_test.py:473-480 for U users at once (the loop of
+ * :345 around it): user u's problem is the row stack [mc_u (N_u committee
+ * items offsets[u] .. offsets[u+1]); hc_u (Nh_u rows offsets_h[u] ..
+ * offsets_h[u+1] of the stacked tables)] over the rows still alive.
+ * hc: [total_h, C] f64 with row stride ld_hc (elements), the users' tables one
+ * after the other; offsets_h: [U+1] int64, DEVICE memory.  excl / excl_h:
+ * optional bitmaps over the global item index / the global hc row index
+ * (ce_excl_words(total_items) / ce_excl_words(total_h) words), NULL = none.
+ * Output slots [u*q, (u+1)*q), user-local positions: i in [0, N_u) is
+ * committee item i, N_u + j is hc row j of that user; order and padding as
+ * everywhere (on an exact tie the lower position wins: the committee item
+ * before the hc row).  A user may have N_u = 0, Nh_u = 0 or both.
+ * One launch, for C = 4 and 1 <= q <= 64 (q = 0 writes nothing); any other
+ * shape returns CE_EUNSUPPORTED: compose it from ce_select_batched_excl over
+ * either part and ce_topq_merge per user.
+ */
+size_t ce_select_batched_mix_workspace_bytes(int64_t total_items, int64_t total_h, int32_t U, int32_t q);
+int ce_select_batched_mix(const void *p, ce_dtype dt, int64_t total_items, int32_t M, int32_t C,
+                          int64_t sN, int64_t sM, int64_t sC, const int64_t *offsets, const double *hc,
+                          int64_t total_h, int64_t ld_hc, const int64_t *offsets_h, int32_t U,
+                          const uint32_t *excl, const uint32_t *excl_h, int32_t q, void *ws,
+                          size_t ws_bytes, double *val_out, int64_t *idx_out, ce_stream_t stream);
+
+/*
+ * Marks the picks of a batched selection -- amg_test.py:484 (the hc frame
+ * drops the queried songs) and :521-531 (X_train does) for U users: idx [U, q]
+ * as ce_select_batched_excl / ce_select_batched_mix wrote it.  Slot (u, k)
+ * with p = idx[u*q + k] >= 0:
+ *   p < N_u:  sets bit g = offsets[u] + p of excl and, when m2h is given and
+ *             m2h[g] >= 0, bit m2h[g] of excl_h;
+ *   else j = p - N_u < Nh_u: sets bit h = offsets_h[u] + j of excl_h and, when
+ *             h2m is given and h2m[h] >= 0, bit h2m[h] of excl.
+ * Other slots are ignored.  m2h [total_items] / h2m [total_h] hold GLOBAL
+ * indices (-1: no twin): a song leaves both pools whichever part picked it.
+ * offsets_h, excl_h, m2h, h2m may be NULL (offsets_h and excl_h together; the
+ * maps need both).
+ */
+int ce_mark_selected_batched(const int64_t *idx, int32_t U, int32_t q, const int64_t *offsets,
+                             uint32_t *excl, const int64_t *offsets_h, uint32_t *excl_h,
+                             const int64_t *m2h, const int64_t *h2m, ce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
