@@ -180,6 +180,28 @@ MIX_SIZES = [(0, 0), (0, 5), (5, 0), (1, 1), (300, 1608), (1608, 1300), (2048, 2
 MIX_QS = [1, 10, 64]
 
 
+def mix_stacks(sizes, off, off_h, ent, ent_h, mask, mask_h, masked):
+    """Per user, the alive rows of [mc_u; hc_u]: their oracle entropies and their user-local positions."""
+    out = []
+    for u, (n, nh) in enumerate(sizes):
+        pos = np.flatnonzero(~mask[off[u]:off[u + 1]]) if masked else np.arange(n)
+        hpos = np.flatnonzero(~mask_h[off_h[u]:off_h[u + 1]]) if masked else np.arange(nh)
+        out.append((np.concatenate([ent[off[u] + pos], ent_h[off_h[u] + hpos]]),
+                    np.concatenate([pos, n + hpos]).astype(np.int64)))
+    return out
+
+
+def mix_expected(stacks, q):
+    """The oracle's top q of every user's stack, padded: values [U, q], positions [U, q]."""
+    from oracle import ce_oracle as O
+
+    ev, ei = np.empty((len(stacks), q)), np.empty((len(stacks), q), np.int64)
+    for u, (stack, where) in enumerate(stacks):
+        v, i = O.oracle_topq(stack, q) if len(stack) else (np.zeros(0), np.zeros(0, np.int64))
+        ev[u], ei[u] = pad(v, where[i], q)
+    return ev, ei
+
+
 @pytest.fixture(scope="module")
 def mix_case():
     from oracle import ce_oracle as O
@@ -204,16 +226,9 @@ def mix_case():
     for name, (P, lay) in inputs.items():
         ent = O.oracle_committee_entropy(P, lay)
         for masked in (False, True):
+            stacks = mix_stacks(MIX_SIZES, off, off_h, ent, ent_h, mask, mask_h, masked)
             for q in MIX_QS:
-                ev, ei = np.empty((len(MIX_SIZES), q)), np.empty((len(MIX_SIZES), q), np.int64)
-                for u, (n, nh) in enumerate(MIX_SIZES):
-                    pos = np.flatnonzero(~mask[off[u]:off[u + 1]]) if masked else np.arange(n)
-                    hpos = np.flatnonzero(~mask_h[off_h[u]:off_h[u + 1]]) if masked else np.arange(nh)
-                    stack = np.concatenate([ent[off[u] + pos], ent_h[off_h[u] + hpos]])  # [mc_u; hc_u], alive rows
-                    v, i = O.oracle_topq(stack, q) if len(stack) else (np.zeros(0), np.zeros(0, np.int64))
-                    where = np.concatenate([pos, n + hpos]).astype(np.int64)
-                    ev[u], ei[u] = pad(v, where[i], q)
-                exp[name, masked, q] = (ev, ei)
+                exp[name, masked, q] = mix_expected(stacks, q)
     first_uniform = int(-off_h[4] % 5)  # user 4's first uniform hc row (hc[::5] counts stacked rows)
     return off, off_h, hc, mask, mask_h, inputs, exp, (twin - off[4], 300 + first_uniform, nan_item - off[5])
 
@@ -235,6 +250,53 @@ def test_batched_mix(ce, mix_case, name, masked, q):
         a, b = row.index(twin), row.index(hc_twin)  # the committee item and an hc row: one entropy, bit for bit
         assert a < b and ev[4, a].view(np.int64) == ev[4, b].view(np.int64)
     assert ei[5, 0] == nan_item and np.isnan(ev[5, 0])
+
+
+# every row uniform: more survivors than a block's LDS holds (1024 at most), the overflow branch of the tile
+FLOOD_SIZES = [(1100, 1100), (0, 1100), (1100, 0)]  # under the 2048-slot tile: not the streaming path
+
+
+@pytest.fixture(scope="module")
+def flood_case():
+    from oracle import ce_oracle as O
+
+    off = np.concatenate([[0], np.cumsum([a for a, _ in FLOOD_SIZES])]).astype(np.int64)
+    off_h = np.concatenate([[0], np.cumsum([b for _, b in FLOOD_SIZES])]).astype(np.int64)
+    P64 = np.full((4, int(off[-1]), 4), 0.25)
+    hc = np.full((int(off_h[-1]), 4), 0.25)
+    P64[:, 7] = [0.7, 0.1, 0.1, 0.1]   # user 0: one item and one hc row below the flood
+    hc[3] = [1.0, 0.0, 0.0, 0.0]
+    P32 = np.ascontiguousarray(P64.transpose(1, 0, 2)).astype(np.float32)
+    mask, mask_h = np.zeros(int(off[-1]), bool), np.zeros(int(off_h[-1]), bool)
+    mask[[0, 1]] = True                # user 0's first items and first hc row: the order starts later
+    mask_h[0] = True
+    inputs = {"f32_NMC": (P32, "NMC"), "f64_MNC": (P64, "MNC")}
+    ent_h = O.oracle_table_entropy(hc)
+    stacks = {(name, masked): mix_stacks(FLOOD_SIZES, off, off_h, O.oracle_committee_entropy(P, lay), ent_h, mask,
+                                         mask_h, masked)
+              for name, (P, lay) in inputs.items() for masked in (False, True)}
+    exp = {(name, masked, q): mix_expected(s, q) for (name, masked), s in stacks.items() for q in MIX_QS}
+    return off, off_h, hc, mask, mask_h, inputs, stacks, exp
+
+
+@pytest.mark.parametrize("q", MIX_QS)
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("name", ["f32_NMC", "f64_MNC"])
+def test_batched_mix_overflow(ce, flood_case, name, masked, q):
+    """More than CAP = 1024 rows of a block at the floor: exact keys of every
+    slot and the tree merge, positions over both segments."""
+    off, off_h, hc, mask, mask_h, inputs, stacks, exp = flood_case
+    # what the case rests on: in every non-empty user, more than 1024 alive rows carry the maximal entropy
+    for (n, nh), (stack, _) in zip(FLOOD_SIZES, stacks[name, masked]):
+        assert n + nh > 0 and int((stack == stack.max()).sum()) > 1024
+    P, lay = inputs[name]
+    v, i = ce.ops.select_batched_mix(dev(P), dev(off), dev(hc), dev(off_h), q, lay,
+                                     excl=bitmap(mask) if masked else None, excl_h=bitmap(mask_h) if masked else None)
+    assert ce._lib.load().ce_last_kernel().startswith(b"ce::k_select_tiles_mix<")
+    ev, ei = exp[name, masked, q]
+    assert_same(v, i, ev, ei, (name, masked, q))
+    if not masked:  # user 0: positions in order, the one item below the flood left out
+        assert ei[0].tolist() == [p for p in range(q + 1) if p != 7][:q]
 
 
 # ---------------------------------------------------------------------------
