@@ -54,6 +54,8 @@ SIGNATURES = {
     "ce_segment_mean": (_int, [_vp, _int, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _int, _i64, _vp]),
     "ce_select_frames_workspace_bytes": (_sz, [_i64, _i32]),
     "ce_select_frames": (_int, [_vp, _i32, _i32, _vp, _vp, _i64, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "ce_select_frames_excl": (_int, [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "ce_frames_consensus": (_int, [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "ce_topq_workspace_bytes": (_sz, [_i64, _i32]),
     "ce_topq": (_int, [_vp, _i64, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
     "ce_topq_merge": (_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),

@@ -16,7 +16,13 @@ the conventions of ``SelectionSession``: in mix mode i in [0, N_u) is committee
 item i and N_u + j is row j of the user's table, which keeps its own row order.
 
 Modes:
-  mc    one ``ops.select_batched(excl=)`` and one mark per epoch
+  mc    one ``ops.select_batched(excl=)`` and one mark per epoch.  Built with
+        ``frame_offsets`` (the CSR of the frame rows over the stacked songs,
+        optionally ``frame_perm``), ``step(frames=[...])`` takes the members'
+        FRAME-level outputs: one ``ops.frames_consensus`` over all users'
+        remaining songs writes the committee mean rows (amg_test.py:437-441)
+        into a buffer the session owns, and the selection reads them as a
+        one-member committee -- three launches per epoch, mix included
   hc    the same over the stacked tables as a one-member f64 committee
   mix   one ``ops.select_batched_mix`` and one mark.  ``hc_to_mc`` is a flat
         [total_h] array: per hc row, the user-local committee item of the same
@@ -42,6 +48,7 @@ import torch
 
 from . import ops
 from .select import MODES, _device, _hc_tensor, stack_committee
+from .session import frame_member_tensors
 
 _MIX_KERNEL_MAX_Q = 64  # include/ce.h: ce_select_batched_mix runs C = 4, q <= 64
 
@@ -54,7 +61,8 @@ def _offsets_host(offsets, what):
 
 
 class BatchedSelectionSession:
-    def __init__(self, queries, mode, offsets, *, hc=None, hc_offsets=None, hc_to_mc=None, device=None):
+    def __init__(self, queries, mode, offsets, *, hc=None, hc_offsets=None, hc_to_mc=None, device=None,
+                 frame_offsets=None, frame_perm=None, n_classes=4):
         if mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
         if mode == "rand":
@@ -109,6 +117,27 @@ class BatchedSelectionSession:
                     raise ValueError(f"hc_to_mc maps two hc rows to one committee item (user {u})")
                 h2m_g[rows[ok]] = off[u] + loc[ok]
                 m2h_g[off[u] + loc[ok]] = rows[ok]
+        # frame-level members (step(frames=...)): the CSR of the frame rows over the STACKED songs
+        f_off = f_perm = None
+        if frame_perm is not None and frame_offsets is None:
+            raise ValueError("frame_perm needs frame_offsets")
+        if frame_offsets is not None:
+            if mode == "hc":
+                raise ValueError("frame_offsets (frame-level members) has no use in mode 'hc': it selects from no "
+                                 "committee")
+            f_off = np.asarray(frame_offsets.cpu() if isinstance(frame_offsets, torch.Tensor) else frame_offsets,
+                               dtype=np.int64).reshape(-1)
+            if f_off.shape[0] != int(off[-1]) + 1:
+                raise ValueError(f"frame_offsets must hold total_items + 1 = {int(off[-1]) + 1} entries "
+                                 f"(got {f_off.shape[0]}): the CSR of the frame rows over the stacked songs")
+            if f_off[0] < 0 or (np.diff(f_off) < 0).any():
+                raise ValueError("frame_offsets must be non-decreasing entries >= 0")
+            if frame_perm is not None:
+                f_perm = np.asarray(frame_perm.cpu() if isinstance(frame_perm, torch.Tensor) else frame_perm,
+                                    dtype=np.int64).reshape(-1)
+                if f_perm.shape[0] < f_off[-1] or (f_perm < 0).any():
+                    raise ValueError(f"frame_perm must hold frame_offsets[-1] = {int(f_off[-1])} row indices >= 0")
+            self._F = int(f_off[-1])
         self.remaining = self.n_items.copy()
         # ---- device state
         self.dev = _device(device)
@@ -123,6 +152,14 @@ class BatchedSelectionSession:
             self.h2m = torch.from_numpy(h2m_g).to(self.dev)
             self.m2h = torch.from_numpy(m2h_g).to(self.dev)
             self._n_dev = torch.from_numpy(self.n_items).to(self.dev).unsqueeze(1)
+        self.frame_offsets = self.frame_perm = self._cons = None
+        if f_off is not None:
+            self.frame_offsets = torch.from_numpy(f_off).to(self.dev)
+            self.frame_perm = torch.from_numpy(f_perm).to(self.dev) if f_perm is not None else None
+            # the consensus rows of every user's remaining songs (ops.frames_consensus writes no row of an
+            # excluded song): allocated and zeroed once, so an epoch allocates nothing
+            C = self.H.shape[1] if mode == "mix" else int(n_classes)
+            self._cons = torch.zeros((int(off[-1]), C), dtype=torch.float64, device=self.dev)
 
     def _slots(self):
         """Output slots per user: q, but never more than the largest user's
@@ -139,17 +176,36 @@ class BatchedSelectionSession:
             raise ValueError(f"committee covers {n} items, the users' pools hold {self._off[-1]}")
         return P, lay
 
-    def step(self, committee=None, layout="MNC", *, _compose=False):
+    def _consensus(self, frames):
+        """frames -> the consensus rows of the remaining songs of every user
+        (one launch), as a one-member committee ((+0.0 + x) / 1 is x)."""
+        total = int(self._off[-1])
+        ts, sl = frame_member_tensors(frames, total, self._F, self.frame_perm is None, self.dev)
+        if ts[0].shape[1] != self._cons.shape[1]:
+            raise ValueError(f"members have {ts[0].shape[1]} classes, the session was built for {self._cons.shape[1]}")
+        ops.frames_consensus(ts, self.frame_offsets, self.frame_perm, sl, excl=self.excl, out=self._cons)
+        return self._cons.unsqueeze(1), "NMC"
+
+    def step(self, committee=None, layout="MNC", *, frames=None, _compose=False):
         """One epoch on the device: selects every user's picks among their
         remaining songs and marks them.  Returns idx [U, slots] (int64 device
         tensor, -1 padding); nothing is synchronised and ``remaining`` is not
-        touched -- ``account`` does that once the picks are on the host."""
+        touched -- ``account`` does that once the picks are on the host.
+        ``frames`` (a session built with ``frame_offsets``; instead of
+        ``committee``): the members' outputs over every user's frame rows,
+        [F, C] frame-level or [total_items, C] song-level; three launches
+        (consensus rows, select, mark) for any number of users and members."""
+        if frames is not None:
+            if committee is not None:
+                raise ValueError("pass `committee` or `frames`, not both")
+            if self._cons is None:
+                raise ValueError("`frames` needs a session built with frame_offsets (the frame rows' CSR)")
         qs = self._slots()
         if self.mode == "hc":
             _, idx = ops.select_batched(self.H.unsqueeze(1), self.offsets, qs, "NMC", excl=self.excl)
             ops.mark_selected_batched(idx, self.offsets, self.excl)
             return idx
-        P, lay = self._committee(committee, layout)
+        P, lay = self._consensus(frames) if frames is not None else self._committee(committee, layout)
         if self.mode == "mc":
             _, idx = ops.select_batched(P, self.offsets, qs, lay, excl=self.excl)
             ops.mark_selected_batched(idx, self.offsets, self.excl)
@@ -195,9 +251,9 @@ class BatchedSelectionSession:
                 self.remaining[u] -= len(r)
         return out
 
-    def select(self, committee=None, layout="MNC", *, _compose=False):
+    def select(self, committee=None, layout="MNC", *, frames=None, _compose=False):
         """One epoch: a list of U int64 arrays -- each user's picked positions
         in their full pool, best first, fewer when a pool runs dry -- and the
         picks leave the pools.  _compose (private, tests): force the composed
         mix path."""
-        return self.account(self.step(committee, layout, _compose=_compose))
+        return self.account(self.step(committee, layout, frames=frames, _compose=_compose))

@@ -378,16 +378,12 @@ class _Member(ctypes.Structure):
                 ("ld", ctypes.c_int64)]
 
 
-def select_frames(members, offsets, q, perm=None, base_idx=0, song_level=None):
-    """amg_test.py:426-445 from the members' FRAME-level outputs in one pass
-    (ce_select_frames, SURVEY.md §8(f)1): per member the groupby(['s_id'])
-    mean (:437), the member-sequential mean over the stack, the entropy and the
-    top-q over songs -- the [M, N, C] stack is never written.  ``members``:
-    device tensors [F, C] (frame rows, song n = rows perm[offsets[n]:
-    offsets[n+1]] or offsets[n]:offsets[n+1]) or [N, C] (song-level, e.g. the
-    CNN member); ``song_level`` overrides the shape rule per member.  Any q:
-    q <= 64 in one pass; larger q through the per-song entropies.
-    Returns (vals [q], idx [q]) over the N sorted songs."""
+def _frame_members(members, offsets, perm, song_level):
+    """The member and shape rules of the frames entry points: (ce_member array,
+    the tensors it points into, C, N, offsets, perm).  ``members``: device
+    tensors [F, C] (frame rows) or [N, C] (song-level); ``song_level`` overrides
+    the shape rule per member.  With ``perm`` or ``song_level`` given nothing is
+    read back from the device."""
     members = list(members)
     if not members:
         raise ValueError("committee has no members")
@@ -399,7 +395,6 @@ def select_frames(members, offsets, q, perm=None, base_idx=0, song_level=None):
     if perm is not None:
         _on_gpu(perm, "perm")
         perm = perm.to(torch.int64).contiguous()
-    q = _check_q(q)
     C = members[0].shape[1]
     for m, t in enumerate(members):
         _on_gpu(t, f"member {m}")
@@ -416,6 +411,8 @@ def select_frames(members, offsets, q, perm=None, base_idx=0, song_level=None):
         if len(fr) > 1:
             raise ValueError(f"frame-level members disagree on the frame count: {sorted(fr)}")
         F = fr.pop() if fr else None
+    if F is None and song_level is not None:  # every member flagged song-level: no frame row is read
+        F = 0
     if F is None:  # every member has N rows: only the offsets tell
         F = int(offsets[-1])
     arr = (_Member * len(members))()
@@ -436,12 +433,59 @@ def select_frames(members, offsets, q, perm=None, base_idx=0, song_level=None):
             raise ValueError(f"member {m} has {t.shape[0]} rows; a {'song' if sl else 'frame'}-level member needs "
                              f">= {need}")
         arr[m] = _Member(t.data_ptr(), _DT[t.dtype], 1 if sl else 0, t.stride(0))
+    return arr, keep, C, N, offsets, perm
+
+
+def select_frames(members, offsets, q, perm=None, base_idx=0, song_level=None, excl=None):
+    """amg_test.py:426-445 from the members' FRAME-level outputs in one pass
+    (ce_select_frames, SURVEY.md §8(f)1): per member the groupby(['s_id'])
+    mean (:437), the member-sequential mean over the stack, the entropy and the
+    top-q over songs -- the [M, N, C] stack is never written.  ``members``:
+    device tensors [F, C] (frame rows, song n = rows perm[offsets[n]:
+    offsets[n+1]] or offsets[n]:offsets[n+1]) or [N, C] (song-level, e.g. the
+    CNN member); ``song_level`` overrides the shape rule per member.  Any q:
+    q <= 64 in one pass; larger q through the per-song entropies.  excl: an
+    optional exclusion bitmap over the songs (excl_bitmap(N); bit n set = song
+    n is out of the pool, whatever base_idx): the selection runs over the
+    others inside the same kernels (ce_select_frames_excl) -- a session's
+    epoch without rebuilding the offsets.
+    Returns (vals [q], idx [q]) over the N sorted songs."""
+    arr, keep, C, N, offsets, perm = _frame_members(members, offsets, perm, song_level)
+    q = _check_q(q)
     lib = _lib.load()
     ws = WORKSPACE.get(offsets.device, lib.ce_select_frames_workspace_bytes(N, q), _sort_path(q))
     vals, idx = _outs(q, offsets.device)
-    call("ce_select_frames", ctypes.cast(arr, ctypes.c_void_p), len(members), C, _p(offsets), _p(perm), N, q,
-         int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx), _stream(offsets.device))
+    if excl is None:
+        call("ce_select_frames", ctypes.cast(arr, ctypes.c_void_p), len(keep), C, _p(offsets), _p(perm), N, q,
+             int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx), _stream(offsets.device))
+    else:
+        _check_excl(excl, N)
+        call("ce_select_frames_excl", ctypes.cast(arr, ctypes.c_void_p), len(keep), C, _p(offsets), _p(perm), N,
+             _p(excl), q, int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx), _stream(offsets.device))
     return vals, idx
+
+
+def frames_consensus(members, offsets, perm=None, song_level=None, excl=None, out=None):
+    """amg_test.py:426-441 from the members' FRAME-level outputs: the committee
+    mean consensus_prob [N, C] float64 (ce_frames_consensus) -- per member the
+    groupby(['s_id']) mean (:437), then the member-sequential mean over the
+    stack (:441), the [M, N, C] stack never written.  Members, offsets, perm
+    and song_level as select_frames.  excl: an optional exclusion bitmap over
+    the songs; rows of excluded songs are NOT written (``out`` keeps what it
+    held; a new tensor is zero there) and their frames are not read.  out: an
+    optional float64 [N, C] view with unit column stride (any row stride).
+    Nothing is synchronised when ``perm`` or ``song_level`` is given."""
+    arr, keep, C, N, offsets, perm = _frame_members(members, offsets, perm, song_level)
+    if out is None:
+        out = (torch.zeros if excl is not None else torch.empty)((N, C), dtype=torch.float64, device=offsets.device)
+    _on_gpu(out, "out")
+    if out.dtype != torch.float64 or out.dim() != 2 or tuple(out.shape) != (N, C) or (C > 1 and out.stride(1) != 1):
+        raise ValueError(f"out must be a float64 [N={N}, C={C}] view with unit column stride")
+    if excl is not None:
+        _check_excl(excl, N)
+    call("ce_frames_consensus", ctypes.cast(arr, ctypes.c_void_p), len(keep), C, _p(offsets), _p(perm), N, _p(excl),
+         _p(out), out.stride(0) if N > 1 else max(out.stride(0), C), _stream(offsets.device))
+    return out
 
 
 def _f64_dev(t, device, what):

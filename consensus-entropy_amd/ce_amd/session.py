@@ -15,7 +15,14 @@ the caller maps them to song ids once.  Selection per epoch equals the
 reference's on the shrunken pool (tests/test_gpu_parity.py::test_session_*).
 
 Modes (amg_test.py:425-489):
-  mc    committee over the full pool [M, N, C] (or [N, M, C]), excluding queried items
+  mc    committee over the full pool [M, N, C] (or [N, M, C]), excluding queried items;
+        or, built with ``s_id`` (the song id of every frame row of the full
+        X_train), the members' FRAME-level outputs: ``select(frames=[...])`` runs
+        the groupby mean (:437), the committee mean, the entropy and the top-q
+        over the remaining songs in one launch (ops.select_frames(excl=)), with
+        no [M, N, C] stack and no offsets rebuilt as the pool shrinks.  In mix
+        the frames give the consensus rows (ops.frames_consensus) the mix reads.
+        Positions then index ``song_ids`` (the sorted unique ids, :437's rows)
   hc    the human-consensus table, fixed at construction, excluding queried rows
   mix   both.  The hc table keeps the reference's OWN row order (annotation
         order, :359/:376), not the committee's (sorted s_id, :437), so the
@@ -42,12 +49,31 @@ import numpy as np
 import torch
 
 from . import ops
-from .select import MODES, _device, _hc_tensor, stack_committee
+from .select import MODES, _device, _hc_tensor, song_groups, stack_committee
+
+
+def frame_member_tensors(frames, n_songs, n_frames, grouped, dev):
+    """Members handed to a session as ``frames=``: device tensors and their
+    song-level flags by committee_from_frames' rule -- [F, C] rows in X_train
+    order are frame-level, [N, C] rows song-level (F == N with the frames
+    already grouped: song-level, each song being its one frame)."""
+    ts, sl = [], []
+    for m, a in enumerate(frames):
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(getattr(a, "values", a)))
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        if t.dim() != 2 or t.shape[0] not in (n_frames, n_songs):
+            raise ValueError(f"member {m} has shape {tuple(t.shape)}: neither {n_frames} frames nor {n_songs} songs")
+        ts.append(t.to(dev))
+        sl.append(not (t.shape[0] == n_frames and (n_frames != n_songs or not grouped)))
+    if not ts:
+        raise ValueError("committee has no members")
+    return ts, sl
 
 
 class SelectionSession:
     def __init__(self, queries, mode, n_items, *, hc=None, votes=None, hc_to_mc=None, rng=None, device=None,
-                 n_classes=4, rand_order=None):
+                 n_classes=4, rand_order=None, s_id=None):
         if mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
         self.q = int(queries)
@@ -55,6 +81,18 @@ class SelectionSession:
             raise ValueError(f"queries = {self.q} is negative")
         self.mode = mode
         self.N = int(n_items)
+        # frame-level members (select(frames=...)): the groupby geometry of the
+        # FULL X_train, computed once; checked on the host before any device work
+        self.song_ids = None
+        geom = None
+        if s_id is not None:
+            if mode in ("hc", "rand"):
+                raise ValueError(f"s_id (frame-level members) has no use in mode {mode!r}: it selects from no committee")
+            geom = song_groups(s_id)
+            if len(geom[0]) != self.N:
+                raise ValueError(f"s_id names {len(geom[0])} songs, n_items is {self.N}")
+            self.song_ids = geom[0]
+            self._F = int(geom[1][-1])
         self.dev = _device(device)
         self.rng = rng
         self.H = None
@@ -64,6 +102,12 @@ class SelectionSession:
                 self.N = self.H.shape[0]
         self.excl = ops.excl_bitmap(self.N, self.dev)
         self.n_selected = 0
+        if geom is not None:
+            self._f_off = torch.from_numpy(geom[1]).to(self.dev)
+            self._f_perm = torch.from_numpy(geom[2]).to(self.dev) if geom[2] is not None else None
+            # mix: the consensus rows of the remaining songs, a one-member committee for the mix path
+            self._cons = (torch.zeros((self.N, self.H.shape[1]), dtype=torch.float64, device=self.dev)
+                          if mode == "mix" else None)
         self.rand_order = None
         if mode == "rand":
             order = np.arange(self.N) if rand_order is None else np.asarray(rand_order, dtype=np.int64).reshape(-1)
@@ -100,6 +144,19 @@ class SelectionSession:
             raise ValueError(f"committee covers {n} items, the session's pool has {self.N}")
         return ops.select_mc(P, q, lay, excl=self.excl)
 
+    def _mc_frames(self, frames, q):
+        """The committee part from frame-level members.  mc: the fused frames
+        selection with the bitmap (one launch, no stack).  mix: the consensus
+        rows of the remaining songs into the session's buffer, selected as a
+        one-member committee ((+0.0 + x) / 1 is x)."""
+        ts, sl = frame_member_tensors(frames, self.N, self._F, self._f_perm is None, self.dev)
+        if self.mode == "mc":
+            return ops.select_frames(ts, self._f_off, q, perm=self._f_perm, song_level=sl, excl=self.excl)
+        if ts[0].shape[1] != self._cons.shape[1]:
+            raise ValueError(f"members have {ts[0].shape[1]} classes, the hc table {self._cons.shape[1]}")
+        ops.frames_consensus(ts, self._f_off, self._f_perm, sl, excl=self.excl, out=self._cons)
+        return ops.select_mc(self._cons.unsqueeze(1), q, "NMC", excl=self.excl)
+
     def _hc(self, q, excl=None):
         return ops.select_mc(self.H.unsqueeze(1), q, "NMC", excl=self.excl if excl is None else excl)
 
@@ -109,9 +166,18 @@ class SelectionSession:
         n = self.N + (self.Nh if self.mode == "mix" else 0)
         return min(self.q, n)
 
-    def select(self, committee=None, layout="MNC"):
+    def select(self, committee=None, layout="MNC", frames=None):
         """One epoch: returns the q picked positions (np.int64; fewer when the
-        pool runs dry) and removes them from the pool."""
+        pool runs dry) and removes them from the pool.  ``frames`` (a session
+        built with ``s_id``; instead of ``committee``): the members' outputs
+        over the FULL X_train as in select_from_frames -- [F, C] frame rows or
+        [N, C] song-level, device tensors or arrays; positions index
+        ``song_ids``."""
+        if frames is not None:
+            if committee is not None:
+                raise ValueError("pass `committee` or `frames`, not both")
+            if self.song_ids is None:
+                raise ValueError("`frames` needs a session built with s_id (the frame rows' song ids)")
         q = self.q
         if self.mode == "rand":  # amg_test.py:487-489 over the remaining songs, in X_train order
             keep = ~self._mask()
@@ -123,17 +189,17 @@ class SelectionSession:
             return pick
         qs = self._slots()
         if self.mode == "mc":
-            if committee is None:
-                raise ValueError("mc mode needs `committee`")
-            _, idx = self._mc(committee, layout, qs)
+            if committee is None and frames is None:
+                raise ValueError("mc mode needs `committee` (or `frames`)")
+            _, idx = self._mc_frames(frames, qs) if frames is not None else self._mc(committee, layout, qs)
             ops.mark_selected(self.excl, self.N, idx)
         elif self.mode == "hc":
             _, idx = self._hc(qs)
             ops.mark_selected(self.excl, self.N, idx)
         else:  # mix: top-q of each part over the remaining songs, then the union's top-q
-            if committee is None:
-                raise ValueError("mix mode needs `committee`")
-            vm, im = self._mc(committee, layout, qs)
+            if committee is None and frames is None:
+                raise ValueError("mix mode needs `committee` (or `frames`)")
+            vm, im = self._mc_frames(frames, qs) if frames is not None else self._mc(committee, layout, qs)
             vh, ih = self._hc(qs, self.excl_hc)
             ih = torch.where(ih >= 0, ih + self.N, ih)
             _, idx = ops.topq_merge(torch.cat([vm, vh]), torch.cat([im, ih]), qs)

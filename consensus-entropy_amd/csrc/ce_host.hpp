@@ -220,16 +220,17 @@ static inline int sort_entropies(const WsLayout& L, void* ws, const CommArgs& a,
 }
 
 // an entropy vector -> the top q: the block lists + a merge, or the sort path
-// (the caller has run check_sort_n for q > CE_MAX_Q)
+// (the caller has run check_sort_n for q > CE_MAX_Q); excl: items whose bit
+// is set are out (their ent is not read as a candidate), or nullptr
 static inline void select_entropies(const WsLayout& L, void* ws, const double* ent, int64_t N, int q, int64_t base_idx,
-                                    double* oval, int64_t* oidx, hipStream_t st) {
+                                    double* oval, int64_t* oidx, hipStream_t st, const uint32_t* excl = nullptr) {
     if (q > CE_MAX_Q) {
-        sort_select(sort_view(L, ws), ent, N, base_idx, nullptr, q, oval, oidx, nullptr, st);
+        sort_select(sort_view(L, ws), ent, N, base_idx, excl, q, oval, oidx, nullptr, st);
         return;
     }
     const int G = pool_blocks(N);
     const WsLists w = lists_view(L, ws);
-    Seg sg{nullptr, N, G, base_idx};
+    Seg sg{nullptr, N, G, base_idx, excl};
     partial_entropies(ent, sg, G, q, w, oval, oidx, G == 1, st);
     if (G > 1) launch_finish_lists(w.c, 1, G, q, oval, oidx, st);
 }

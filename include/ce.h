@@ -152,6 +152,43 @@ int ce_select_frames(const ce_member *members, int32_t M, int32_t C, const int64
                      size_t ws_bytes, double *val_out, int64_t *idx_out, ce_stream_t stream);
 
 /*
+ * The same pass for a multi-epoch session (SURVEY.md §8(f)3 over §8(f)1) --
+ * replaces amg_test.py:425-447 of every epoch after the first, where the
+ * reference predicts on the frame rows of what is LEFT of X_train (:521-531
+ * removed the queried songs): the full pool stays on the device and the
+ * exclusion bitmap is tested inside the frames kernels.  excl: ce_excl_words(N)
+ * words, the layout of ce_select_mc_excl -- bit n of word n / 32 set = song n
+ * (its position in sorted s_id order, WITHOUT base_idx) is already queried.
+ * An excluded song reads no frame row, no perm entry and no song-level row and
+ * is never selected; slots past the remaining songs are padding (idx -1, val
+ * NaN).  A song's mean depends on its own frames only and sorted order
+ * survives a subset, so the selection equals the reference's groupby on the
+ * shrunken X_train.  Any q, the routes and the workspace
+ * (ce_select_frames_workspace_bytes) of ce_select_frames.  excl == NULL with
+ * N > 0 is CE_EINVAL.
+ */
+int ce_select_frames_excl(const ce_member *members, int32_t M, int32_t C, const int64_t *offsets,
+                          const int64_t *perm_or_null, int64_t N, const uint32_t *excl, int32_t q,
+                          int64_t base_idx, void *ws, size_t ws_bytes, double *val_out,
+                          int64_t *idx_out, ce_stream_t stream);
+
+/*
+ * The committee mean itself from frame-level members -- replaces
+ * amg_test.py:426-441 (:458-471 in the mix branch): the groupby means of
+ * :437 / :469 and consensus_prob = np.mean(np.array(pred_prob), axis=0), as
+ * f64 rows out[n * ld_out + c] (ld_out >= C), without the [M, N, C] stack.
+ * It feeds the selections that need more than one global top-q (ce_select_mix,
+ * ce_select_batched_excl, ce_select_batched_mix) as a one-member f64 committee:
+ * (+0.0 + x) / 1 is x, so those selections stay the reference's.  Members and
+ * C as ce_select_frames.  excl_or_null: rows of excluded songs are NOT written
+ * (the caller's buffer keeps what it held) and their frames are not read.  No
+ * workspace.
+ */
+int ce_frames_consensus(const ce_member *members, int32_t M, int32_t C, const int64_t *offsets,
+                        const int64_t *perm_or_null, int64_t N, const uint32_t *excl_or_null,
+                        double *out, int64_t ld_out, ce_stream_t stream);
+
+/*
  * Committee member inference on the device -- the
  * predict_proba of the reference's linear members (amg_test.py:435, :467;
  * deam_classifier.py:211-218) over frames X [F, D] f64 (row stride ld),
