@@ -142,6 +142,7 @@ static int launch_stream_impl(const CommArgs& a, int G, int q, int64_t base_idx,
         });
     });
     if (rc == CE_OK) return folded;
+    if (a.C > kWideMaxC) return 0;  // before pw_plan: its leaf arrays are sized for C <= kWideMaxC
     const WideArgs wa = wide_args(a);
     const PwPlan pl = pw_plan(a.C);
     const size_t lds = wide_lds_bytes(a.C);

@@ -151,6 +151,42 @@ def test_any_q_without_gpu():
     assert lib.ce_select_mc(p, 0, N, 16, 4, 64, 4, 1, -5, 0, p, ws, p, p, None) == _lib.CE_EINVAL
 
 
+def test_class_count_past_the_wide_limit_is_refused_without_gpu():
+    """C > 2048 (kWideMaxC) has no kernel: CE_EUNSUPPORTED from the entropy and
+    from every selecting path, on the host, before anything launches -- and
+    before the wide kernels' pairwise-summation plan is built: its leaf arrays
+    hold the 32 leaves of C <= 2048, and building it for C = 4095 (33 leaves) or
+    2^20 wrote past them on the host stack."""
+    from ce_amd import _lib
+
+    lib = _lib.load()
+    p = ctypes.c_void_p(256)
+    N, M = 100, 2
+    for C in (2049, 4095, 4097, 100_000, 1 << 20):
+        for dt in (0, 1, 2):
+            assert lib.ce_committee_entropy(p, dt, N, M, C, M * C, C, 1, None, p, None) == _lib.CE_EUNSUPPORTED, (C, dt)
+            for q in (10, 65):  # the streaming ladder, the block lists
+                ws = lib.ce_select_mc_workspace_bytes(N, q)
+                rc = lib.ce_select_mc(p, dt, N, M, C, M * C, C, 1, q, 0, p, ws, p, p, None)
+                assert rc == _lib.CE_EUNSUPPORTED and b"no kernel" in lib.ce_last_error(), (C, dt, q)
+                assert lib.ce_last_kernel() == b""
+
+
+def test_empty_committee_entropy_takes_null_pointers_without_gpu():
+    """ce_committee_entropy over N = 0 items is no error with null pointers (an
+    empty device tensor's data pointer is null), as on the selecting entry
+    points; a null ent with items to score still is."""
+    from ce_amd import _lib
+
+    lib = _lib.load()
+    p = ctypes.c_void_p(256)
+    for dt in (0, 1, 2):
+        for C in (4, 9):
+            assert lib.ce_committee_entropy(None, dt, 0, 3, C, 3 * C, C, 1, None, None, None) == _lib.CE_OK
+    assert lib.ce_committee_entropy(p, 0, 10, 3, 4, 12, 4, 1, None, None, None) == _lib.CE_EINVAL
+    assert b"null ent" in lib.ce_last_error()
+
+
 def test_sort_path_rejects_2pow32_records_without_gpu():
     """The radix sort counts records in 32 bits (ce_launch_sort.hip): a pool of
     2^32 items or more with q > CE_MAX_Q is refused, not mis-sorted; batched
