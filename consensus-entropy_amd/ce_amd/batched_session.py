@@ -47,16 +47,20 @@ import numpy as np
 import torch
 
 from . import ops
-from .select import MODES, _device, _hc_tensor, stack_committee
-from .session import frame_member_tensors
+from .select import MODES, _device, _hc_tensor, frame_member_tensors, stack_committee
+from .session import songs_leaving, twin_maps
 
 _MIX_KERNEL_MAX_Q = 64  # include/ce.h: ce_select_batched_mix runs C = 4, q <= 64
 
 
-def _offsets_host(offsets, what):
+def _offsets_host(offsets, what, n=None, count="U + 1 >= 2"):
+    """Offsets as an int64 host array: `n` entries when given (at least 2
+    otherwise), non-decreasing and >= 0."""
     o = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64).reshape(-1)
-    if o.shape[0] < 2 or o[0] < 0 or (np.diff(o) < 0).any():
-        raise ValueError(f"{what} must hold U + 1 >= 2 non-decreasing entries >= 0")
+    if n is not None and o.shape[0] != n:
+        raise ValueError(f"{what} must hold {count} = {n} entries (got {o.shape[0]})")
+    if (n is None and o.shape[0] < 2) or o[0] < 0 or (np.diff(o) < 0).any():
+        raise ValueError(f"{what} must hold {count} non-decreasing entries >= 0")
     return o
 
 
@@ -94,29 +98,7 @@ class BatchedSelectionSession:
         self.n_rows = np.diff(off_h) if mode == "mix" else None
         h2m_g = m2h_g = None
         if mode == "mix":
-            total_h = int(hc.shape[0])
-            if hc_to_mc is None:
-                if not np.array_equal(off_h, off):
-                    raise ValueError("mix: pass hc_to_mc (user-local committee item of each hc row) when "
-                                     "hc_offsets differ from offsets")
-                h2m = np.concatenate([np.arange(n) for n in self.n_items] + [np.zeros(0, np.int64)])
-            else:
-                h2m = np.asarray(hc_to_mc, dtype=np.int64).reshape(-1)
-            if h2m.shape[0] != total_h:
-                raise ValueError(f"hc_to_mc must hold one entry per hc row ({total_h})")
-            self._h2m_local = h2m
-            h2m_g = np.full(total_h, -1, np.int64)
-            m2h_g = np.full(int(off[-1]), -1, np.int64)
-            for u in range(self.U):
-                rows = np.arange(off_h[u], off_h[u + 1])
-                loc = h2m[rows]
-                if (loc >= self.n_items[u]).any() or (loc < -1).any():
-                    raise ValueError(f"hc_to_mc must give, per hc row, a committee item in [0, N_u) or -1 (user {u})")
-                ok = loc >= 0
-                if len(np.unique(loc[ok])) != ok.sum():
-                    raise ValueError(f"hc_to_mc maps two hc rows to one committee item (user {u})")
-                h2m_g[rows[ok]] = off[u] + loc[ok]
-                m2h_g[off[u] + loc[ok]] = rows[ok]
+            self._h2m_local, h2m_g, m2h_g = twin_maps(hc_to_mc, off, off_h)
         # frame-level members (step(frames=...)): the CSR of the frame rows over the STACKED songs
         f_off = f_perm = None
         if frame_perm is not None and frame_offsets is None:
@@ -125,13 +107,7 @@ class BatchedSelectionSession:
             if mode == "hc":
                 raise ValueError("frame_offsets (frame-level members) has no use in mode 'hc': it selects from no "
                                  "committee")
-            f_off = np.asarray(frame_offsets.cpu() if isinstance(frame_offsets, torch.Tensor) else frame_offsets,
-                               dtype=np.int64).reshape(-1)
-            if f_off.shape[0] != int(off[-1]) + 1:
-                raise ValueError(f"frame_offsets must hold total_items + 1 = {int(off[-1]) + 1} entries "
-                                 f"(got {f_off.shape[0]}): the CSR of the frame rows over the stacked songs")
-            if f_off[0] < 0 or (np.diff(f_off) < 0).any():
-                raise ValueError("frame_offsets must be non-decreasing entries >= 0")
+            f_off = _offsets_host(frame_offsets, "frame_offsets", int(off[-1]) + 1, "total_items + 1")
             if frame_perm is not None:
                 f_perm = np.asarray(frame_perm.cpu() if isinstance(frame_perm, torch.Tensor) else frame_perm,
                                     dtype=np.int64).reshape(-1)
@@ -242,11 +218,8 @@ class BatchedSelectionSession:
             r = rows[u][rows[u] >= 0]
             out.append(r)
             if self.mode == "mix":
-                # songs leaving the committee pool (an hc pick of a song outside it leaves only the table;
-                # a song picked through both parts in one epoch leaves once)
-                n = self.n_items[u]
-                via_hc = self._h2m_local[self._off_h[u] + r[r >= n] - n]
-                self.remaining[u] -= len(np.unique(np.concatenate([r[r < n], via_hc[via_hc >= 0]])))
+                self.remaining[u] -= songs_leaving(r, self.n_items[u],
+                                                   self._h2m_local[self._off_h[u]:self._off_h[u + 1]])
             else:
                 self.remaining[u] -= len(r)
         return out

@@ -35,6 +35,21 @@ def _on_gpu(t, what):
         raise ValueError(f"{what} must live on a HIP device (got {t.device}); there is no CPU path")
 
 
+def _i64(t, what):
+    """An index tensor (offsets, perm, picks) as the C-ABI reads it: on the device, int64, contiguous."""
+    _on_gpu(t, what)
+    if t.dtype == torch.int64 and t.is_contiguous():  # the usual case, without two dispatches
+        return t
+    return t.to(torch.int64).contiguous()
+
+
+def _indexed(device):
+    """torch.device(device); one without an index becomes the current device."""
+    if not isinstance(device, torch.device):
+        device = torch.device(device)
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
 WS_HEADER_BYTES = 65536 + 256  # include/ce.h: the 64 KiB counter header (+ the 256-B alignment carve)
 
 
@@ -145,9 +160,7 @@ class _WorkspaceCache:
         self._warned = False
 
     def get(self, device, nbytes, transient=False):
-        device = torch.device(device)
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _indexed(device)
         with torch.cuda.device(device):  # the capture state of THIS device's current stream
             capturing = torch.cuda.is_current_stream_capturing()
         if capturing:
@@ -203,9 +216,7 @@ def reserve_graph_workspace(nbytes, device=None):
     can hand out `nbytes` of pre-zeroed workspace on `device` (eager only).
     Size it with the ce_*_workspace_bytes functions, one carve per stream per
     capture."""
-    device = torch.device(device if device is not None else "cuda")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _indexed(device if device is not None else "cuda")
     with torch.cuda.device(device):
         WORKSPACE.arena.reserve(device, int(nbytes))
 
@@ -342,6 +353,14 @@ def va_table(va):
     return freq, ent
 
 
+def _csr(offsets, perm):
+    """(offsets, perm, N) of a CSR over N songs, as the C-ABI reads them."""
+    offsets = _i64(offsets, "offsets")
+    if offsets.numel() < 1:
+        raise ValueError("offsets must hold N + 1 entries")
+    return offsets, (_i64(perm, "perm") if perm is not None else None), offsets.numel() - 1
+
+
 def segment_mean(frames, offsets, perm=None, out=None):
     """amg_test.py:437 groupby(['s_id']).mean() of one member on the device
     (pandas 1.1.5 group_mean: f64 sequential sums in row order, NaN skipped,
@@ -350,19 +369,13 @@ def segment_mean(frames, offsets, perm=None, out=None):
     out: optional [N, C] f32/f64 view with unit column stride (e.g. member m of
     a committee stack); default a new tensor of the frames' dtype."""
     _on_gpu(frames, "frames")
-    _on_gpu(offsets, "offsets")
+    _on_gpu(offsets, "offsets")  # refused before a bad frames shape is; _csr does the rest
     if frames.dim() != 2 or frames.dtype not in (torch.float32, torch.float64):
         raise ValueError("frames must be a 2-D float32/float64 tensor [F, C]")
     if frames.stride(1) != 1:
         frames = frames.contiguous()
-    offsets = offsets.to(torch.int64).contiguous()
     F, C = frames.shape
-    N = offsets.numel() - 1
-    if N < 0:
-        raise ValueError("offsets must hold N + 1 entries")
-    if perm is not None:
-        _on_gpu(perm, "perm")
-        perm = perm.to(torch.int64).contiguous()
+    offsets, perm, N = _csr(offsets, perm)
     if out is None:
         out = torch.empty((N, C), dtype=frames.dtype, device=frames.device)
     if out.dim() != 2 or tuple(out.shape) != (N, C) or out.stride(1) != 1 or out.dtype not in _DT:
@@ -387,14 +400,7 @@ def _frame_members(members, offsets, perm, song_level):
     members = list(members)
     if not members:
         raise ValueError("committee has no members")
-    _on_gpu(offsets, "offsets")
-    offsets = offsets.to(torch.int64).contiguous()
-    N = offsets.numel() - 1
-    if N < 0:
-        raise ValueError("offsets must hold N + 1 entries")
-    if perm is not None:
-        _on_gpu(perm, "perm")
-        perm = perm.to(torch.int64).contiguous()
+    offsets, perm, N = _csr(offsets, perm)
     C = members[0].shape[1]
     for m, t in enumerate(members):
         _on_gpu(t, f"member {m}")
@@ -452,16 +458,9 @@ def select_frames(members, offsets, q, perm=None, base_idx=0, song_level=None, e
     Returns (vals [q], idx [q]) over the N sorted songs."""
     arr, keep, C, N, offsets, perm = _frame_members(members, offsets, perm, song_level)
     q = _check_q(q)
-    lib = _lib.load()
-    ws = WORKSPACE.get(offsets.device, lib.ce_select_frames_workspace_bytes(N, q), _sort_path(q))
-    vals, idx = _outs(q, offsets.device)
-    if excl is None:
-        call("ce_select_frames", ctypes.cast(arr, ctypes.c_void_p), len(keep), C, _p(offsets), _p(perm), N, q,
-             int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx), _stream(offsets.device))
-    else:
-        _check_excl(excl, N)
-        call("ce_select_frames_excl", ctypes.cast(arr, ctypes.c_void_p), len(keep), C, _p(offsets), _p(perm), N,
-             _p(excl), q, int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx), _stream(offsets.device))
+    ws, vals, idx = _scratch(offsets.device, q, _lib.load().ce_select_frames_workspace_bytes(N, q))
+    _call_excl("ce_select_frames", (ctypes.cast(arr, ctypes.c_void_p), len(keep), C, _p(offsets), _p(perm), N), excl, N,
+               (q, int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx), _stream(offsets.device)))
     return vals, idx
 
 
@@ -495,14 +494,20 @@ def _f64_dev(t, device, what):
     return t.contiguous()
 
 
+def _check_X(X, dtypes=(torch.float64,)):
+    """The frames X of a member's predict_proba: [F, D] of one of `dtypes`, unit column stride.  Returns (F, D)."""
+    _on_gpu(X, "X")
+    if X.dim() != 2 or X.dtype not in dtypes or X.stride(1) != 1:
+        names = "/".join(str(d).split(".")[1] for d in dtypes)
+        raise ValueError(f"X must be a {names} [F, D] tensor with unit column stride")
+    return X.shape
+
+
 def gnb_predict_proba(X, theta, var, class_prior, out=None):
     """GaussianNB(...).predict_proba(X) on the device (sklearn 0.24.1 math,
     deam_classifier.py:211; amg_test.py:435).  X [F, D] f64 frames; theta /
     var [C, D] (theta_, var_ -- sigma_ in 0.24), class_prior [C]."""
-    _on_gpu(X, "X")
-    if X.dim() != 2 or X.dtype != torch.float64 or X.stride(1) != 1:
-        raise ValueError("X must be a float64 [F, D] tensor with unit column stride")
-    F, D = X.shape
+    F, D = _check_X(X)
     theta = _f64_dev(theta, X.device, "theta")
     var = _f64_dev(var, X.device, "var")
     C = theta.shape[0]
@@ -529,10 +534,7 @@ def sgd_predict_proba(X, coef, intercept, out=None):
     """SGDClassifier(loss='log').predict_proba(X) on the device (sklearn
     _predict_proba_lr, deam_classifier.py:214; amg_test.py:435).  coef [K, D],
     intercept [K]; K = C (OvR) or 1 (binary, C = 2)."""
-    _on_gpu(X, "X")
-    if X.dim() != 2 or X.dtype != torch.float64 or X.stride(1) != 1:
-        raise ValueError("X must be a float64 [F, D] tensor with unit column stride")
-    F, D = X.shape
+    F, D = _check_X(X)
     coef = _f64_dev(coef, X.device, "coef")
     if coef.dim() == 1:
         coef = coef.unsqueeze(0)
@@ -557,12 +559,9 @@ def xgb_predict_proba(X, forest, out=None, out_dtype=torch.float32):
     exact upcast, ready for a committee stack)."""
     from .xgb import XgbForest
 
-    _on_gpu(X, "X")
-    if X.dim() != 2 or X.dtype not in (torch.float32, torch.float64) or X.stride(1) != 1:
-        raise ValueError("X must be a float32/float64 [F, D] tensor with unit column stride")
+    F, D = _check_X(X, (torch.float32, torch.float64))
     if not isinstance(forest, XgbForest):
         forest = XgbForest.from_json(forest)
-    F, D = X.shape
     if forest.max_feature() >= D:
         raise ValueError(f"the forest splits on feature {forest.max_feature()} but X has {D} columns")
     G, C = forest.n_groups, forest.n_classes
@@ -610,6 +609,21 @@ def _outs(q, device, lead=()):
             torch.empty(lead + (q,), dtype=torch.int64, device=device))
 
 
+def _scratch(device, q, ws_bytes, lead=()):
+    """What a selecting call needs besides its inputs: (workspace of ws_bytes, vals, idx)."""
+    return (WORKSPACE.get(device, ws_bytes, _sort_path(q)), *_outs(q, device, lead))
+
+
+def _call_excl(name, head, excl, n, tail):
+    """call(name, *head, *tail); with a bitmap over n items, the entry point
+    name + "_excl", which takes the bitmap between head and tail."""
+    if excl is None:
+        call(name, *head, *tail)
+    else:
+        _check_excl(excl, n)
+        call(name + "_excl", *head, _p(excl), *tail)
+
+
 def topq(ent, q, base_idx=0):
     """np.argsort(ent)[::-1][:q] under the total order (NaN first, desc, lowest
     index).  Returns (vals [q], idx [q]); idx = -1 marks empty slots."""
@@ -617,9 +631,7 @@ def topq(ent, q, base_idx=0):
     q = _check_q(q)
     ent = ent.contiguous().to(torch.float64)
     N = ent.numel()
-    lib = _lib.load()
-    ws = WORKSPACE.get(ent.device, lib.ce_topq_workspace_bytes(N, q), _sort_path(q))
-    vals, idx = _outs(q, ent.device)
+    ws, vals, idx = _scratch(ent.device, q, _lib.load().ce_topq_workspace_bytes(N, q))
     call("ce_topq", _p(ent), N, q, int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx), _stream(ent.device))
     return vals, idx
 
@@ -647,15 +659,9 @@ def select_mc(P, q, layout="MNC", base_idx=0, excl=None):
     comm = _committee_args(P, layout)
     N = comm[2]
     q = _check_q(q)
-    lib = _lib.load()
-    ws = WORKSPACE.get(P.device, lib.ce_select_mc_workspace_bytes(N, q), _sort_path(q))
-    vals, idx = _outs(q, P.device)
-    if excl is None:
-        call("ce_select_mc", *comm, q, int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx), _stream(P.device))
-    else:
-        _check_excl(excl, N)
-        call("ce_select_mc_excl", *comm, _p(excl), q, int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx),
-             _stream(P.device))
+    ws, vals, idx = _scratch(P.device, q, _lib.load().ce_select_mc_workspace_bytes(N, q))
+    _call_excl("ce_select_mc", comm, excl, N,
+               (q, int(base_idx), _p(ws), ws.numel(), _p(vals), _p(idx), _stream(P.device)))
     return vals, idx
 
 
@@ -675,8 +681,7 @@ def mark_selected(excl, n, idx, base_idx=0):
     """Set the bitmap bits of the selected positions idx (device int64; -1
     slots ignored) -- stream-ordered after the selection that produced them."""
     _check_excl(excl, n)
-    _on_gpu(idx, "idx")
-    idx = idx.to(torch.int64).contiguous()
+    idx = _i64(idx, "idx")
     call("ce_mark_selected", _p(excl), int(n), _p(idx), idx.numel(), int(base_idx), _stream(excl.device))
 
 
@@ -830,29 +835,30 @@ def select_mc_chunks(chunks, q, layout="NMC"):
     return job.result()
 
 
+def _hc_table(hc, C, rows="N_h"):
+    """The hc table as the mix entry points read it: float64 [rows, C], unit column stride."""
+    _on_gpu(hc, "hc table")
+    if hc.dim() != 2 or hc.shape[1] != C:
+        raise ValueError(f"hc table must be [{rows}, {C}]")
+    hc = hc.to(torch.float64)
+    return hc if hc.stride(1) == 1 else hc.contiguous()
+
+
 def select_mix(P, hc, q, layout="MNC"):
     """Fused amg_test.py:473-480: top-q over the row stack [mc (N); hc (N_h)]."""
     comm = _committee_args(P, layout)
     N, C = comm[2], comm[4]
-    _on_gpu(hc, "hc table")
-    if hc.dim() != 2 or hc.shape[1] != C:
-        raise ValueError(f"hc table must be [N_h, {C}]")
-    hc = hc.to(torch.float64)
-    if hc.stride(1) != 1:
-        hc = hc.contiguous()
+    hc = _hc_table(hc, C)
     q = _check_q(q)
     N_h = hc.shape[0]
-    lib = _lib.load()
-    ws = WORKSPACE.get(P.device, lib.ce_select_mix_workspace_bytes(N, N_h, q), _sort_path(q))
-    vals, idx = _outs(q, P.device)
+    ws, vals, idx = _scratch(P.device, q, _lib.load().ce_select_mix_workspace_bytes(N, N_h, q))
     call("ce_select_mix", *comm, _p(hc), N_h, hc.stride(0), q, _p(ws), ws.numel(), _p(vals), _p(idx),
          _stream(P.device))
     return vals, idx
 
 
 def _user_offsets(offsets, what="offsets", U=None):
-    _on_gpu(offsets, what)
-    offsets = offsets.to(torch.int64).contiguous()
+    offsets = _i64(offsets, what)
     if offsets.numel() < 2 or (U is not None and offsets.numel() != U + 1):
         raise ValueError(f"{what} must hold U + 1 >= 2 entries" + (f" (U = {U})" if U is not None else ""))
     return offsets
@@ -869,15 +875,9 @@ def select_batched(P, offsets, q, layout="MNC", excl=None):
     offsets = _user_offsets(offsets)
     U = offsets.numel() - 1
     q = _check_q(q)
-    lib = _lib.load()
-    ws = WORKSPACE.get(P.device, lib.ce_select_batched_workspace_bytes(N, U, q), _sort_path(q))
-    vals, idx = _outs(q, P.device, (U,))
-    if excl is None:
-        call("ce_select_batched", *comm, _p(offsets), U, q, _p(ws), ws.numel(), _p(vals), _p(idx), _stream(P.device))
-    else:
-        _check_excl(excl, N)
-        call("ce_select_batched_excl", *comm, _p(offsets), U, _p(excl), q, _p(ws), ws.numel(), _p(vals), _p(idx),
-             _stream(P.device))
+    ws, vals, idx = _scratch(P.device, q, _lib.load().ce_select_batched_workspace_bytes(N, U, q), (U,))
+    _call_excl("ce_select_batched", (*comm, _p(offsets), U), excl, N,
+               (q, _p(ws), ws.numel(), _p(vals), _p(idx), _stream(P.device)))
     return vals, idx
 
 
@@ -890,12 +890,7 @@ def select_batched_mix(P, offsets, hc, hc_offsets, q, layout="MNC", excl=None, e
     runs C = 4, q <= 64 (CEError otherwise: BatchedSelectionSession composes)."""
     comm = _committee_args(P, layout)
     N, C = comm[2], comm[4]
-    _on_gpu(hc, "hc table")
-    if hc.dim() != 2 or hc.shape[1] != C:
-        raise ValueError(f"hc table must be [total_h, {C}]")
-    hc = hc.to(torch.float64)
-    if hc.stride(1) != 1:
-        hc = hc.contiguous()
+    hc = _hc_table(hc, C, "total_h")
     offsets = _user_offsets(offsets)
     U = offsets.numel() - 1
     hc_offsets = _user_offsets(hc_offsets, "hc_offsets", U)
@@ -905,9 +900,7 @@ def select_batched_mix(P, offsets, hc, hc_offsets, q, layout="MNC", excl=None, e
         _check_excl(excl, N)
     if excl_h is not None:
         _check_excl(excl_h, Nh)
-    lib = _lib.load()
-    ws = WORKSPACE.get(P.device, lib.ce_select_batched_mix_workspace_bytes(N, Nh, U, q), _sort_path(q))
-    vals, idx = _outs(q, P.device, (U,))
+    ws, vals, idx = _scratch(P.device, q, _lib.load().ce_select_batched_mix_workspace_bytes(N, Nh, U, q), (U,))
     call("ce_select_batched_mix", *comm, _p(offsets), _p(hc), Nh, hc.stride(0), _p(hc_offsets), U, _p(excl),
          _p(excl_h), q, _p(ws), ws.numel(), _p(vals), _p(idx), _stream(P.device))
     return vals, idx
@@ -919,12 +912,11 @@ def mark_selected_batched(idx, offsets, excl, hc_offsets=None, excl_h=None, m2h=
     p in excl (and hc row m2h[item] in excl_h), one above it hc row
     hc_offsets[u] + p - N_u in excl_h (and item h2m[row] in excl).  The maps
     hold global indices, -1 = no twin.  Stream-ordered, nothing leaves the GPU."""
-    _on_gpu(idx, "idx")
+    idx = _i64(idx, "idx")
     offsets = _user_offsets(offsets)
     U = offsets.numel() - 1
     if idx.dim() != 2 or idx.shape[0] != U:
         raise ValueError(f"idx must be [U = {U}, q]")
-    idx = idx.to(torch.int64).contiguous()
     _check_excl(excl, 0)
     if hc_offsets is not None:
         hc_offsets = _user_offsets(hc_offsets, "hc_offsets", U)

@@ -80,6 +80,34 @@ def song_groups(s_id):
     return uniq, offsets, perm
 
 
+def groupby_device(s_id, dev):
+    """song_groups(s_id) with its CSR on `dev`: (sorted ids, N songs, F frame
+    rows, offsets [N + 1], the grouping permutation [F] or None)."""
+    uniq, offsets, perm = song_groups(s_id)
+    return (uniq, len(uniq), int(offsets[-1]), torch.from_numpy(offsets).to(dev),
+            torch.from_numpy(perm).to(dev) if perm is not None else None)
+
+
+def frame_member_tensors(frames, n_songs, n_frames, grouped, dev):
+    """The member rule of amg_test.py:430-437, stated once: the members as
+    float32/float64 tensors on `dev` (any other dtype through float64) and
+    their song-level flags -- [F, C] rows in X_train order are frame-level,
+    [N, C] rows song-level (F == N with the frames already grouped: song-level,
+    each song being its one frame)."""
+    ts, sl = [], []
+    for m, a in enumerate(frames):
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(getattr(a, "values", a)))
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        if t.dim() != 2 or t.shape[0] not in (n_frames, n_songs):
+            raise ValueError(f"member {m} has shape {tuple(t.shape)}: neither {n_frames} frames nor {n_songs} songs")
+        ts.append(t.to(dev))
+        sl.append(not (t.shape[0] == n_frames and (n_frames != n_songs or not grouped)))
+    if not ts:
+        raise ValueError("committee has no members")
+    return ts, sl
+
+
 def committee_from_frames(members, s_id, device=None):
     """The committee stack np.array(pred_prob) of amg_test.py:426-441, built on
     the device.  `members` in mod_list order; each is either a frame-level
@@ -89,37 +117,20 @@ def committee_from_frames(members, s_id, device=None):
     (stack [M, N, C] on the device, the sorted song ids of the groupby rows).
     The stack is float64 unless every member is float32 (np.array's rule)."""
     dev = _device(device)
-    uniq, offsets, perm = song_groups(s_id)
-    N = len(uniq)
-    F = len(np.asarray(getattr(s_id, "values", s_id)))
+    uniq, N, F, offs, perm = groupby_device(s_id, dev)
     # members: device tensors (e.g. ops.gnb_predict_proba outputs) stay on the device
-    arrs = [m if isinstance(m, torch.Tensor) else np.asarray(getattr(m, "values", m)) for m in members]
-    if not arrs:
-        raise ValueError("committee has no members")
-    C = arrs[0].shape[1]
-    f32 = [a.dtype in (np.float32, torch.float32) for a in arrs]
-    dt = torch.float32 if all(f32) else torch.float64
-    stack = torch.empty((len(arrs), N, C), dtype=dt, device=dev)
-    offs_d = torch.from_numpy(offsets).to(dev)
-    perm_d = torch.from_numpy(perm).to(dev) if perm is not None else None
-    for m, a in enumerate(arrs):
-        if a.ndim != 2 or a.shape[1] != C:
-            raise ValueError(f"member {m} has shape {tuple(a.shape)}, expected [*, {C}]")
-        if isinstance(a, torch.Tensor):
-            t = a.to(dev)
-            if t.dtype not in (torch.float32, torch.float64):
-                t = t.to(torch.float64)
-        else:
-            t = None
-        if a.shape[0] == F and (F != N or perm is not None):  # frame-level: groupby mean on the device
-            if t is None:
-                t = torch.from_numpy(np.ascontiguousarray(a, dtype=a.dtype if a.dtype in (np.float32, np.float64)
-                                                          else np.float64)).to(dev)
-            ops.segment_mean(t.contiguous(), offs_d, perm_d, out=stack[m])
-        elif a.shape[0] == N:  # song-level member
-            stack[m] = (t if t is not None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)).to(dt)
-        else:
-            raise ValueError(f"member {m} has {a.shape[0]} rows: neither {F} frames nor {N} songs")
+    ts, sl = frame_member_tensors(members, N, F, perm is None, dev)
+    C = ts[0].shape[1]
+    for m, t in enumerate(ts):
+        if t.shape[1] != C:
+            raise ValueError(f"member {m} has shape {tuple(t.shape)}, expected [*, {C}]")
+    dt = torch.float32 if all(t.dtype == torch.float32 for t in ts) else torch.float64
+    stack = torch.empty((len(ts), N, C), dtype=dt, device=dev)
+    for m, t in enumerate(ts):
+        if sl[m]:
+            stack[m] = t.to(dt)
+        else:  # frame-level: groupby mean on the device
+            ops.segment_mean(t.contiguous(), offs, perm, out=stack[m])
     return stack, uniq
 
 
@@ -131,20 +142,9 @@ def select_from_frames(members, s_id, q, device=None):
     never built.  Returns (q_ind positions over the sorted songs, the sorted
     song ids) -- q_songs = ids[q_ind] as :447 maps them."""
     dev = _device(device)
-    uniq, offsets, perm = song_groups(s_id)
-    N, F = len(uniq), len(np.asarray(getattr(s_id, "values", s_id)))
-    ts, sl = [], []
-    for m, a in enumerate(members):
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(getattr(a, "values", a)))
-        if t.dtype not in (torch.float32, torch.float64):
-            t = t.to(torch.float64)
-        if t.dim() != 2 or t.shape[0] not in (F, N):
-            raise ValueError(f"member {m} has shape {tuple(t.shape)}: neither {F} frames nor {N} songs")
-        ts.append(t.to(dev))
-        sl.append(not (t.shape[0] == F and (F != N or perm is not None)))  # committee_from_frames' rule
-    offs = torch.from_numpy(offsets).to(dev)
-    pd_ = torch.from_numpy(perm).to(dev) if perm is not None else None
-    _, idx = ops.select_frames(ts, offs, q, perm=pd_, song_level=sl)
+    uniq, N, F, offs, perm = groupby_device(s_id, dev)
+    ts, sl = frame_member_tensors(members, N, F, perm is None, dev)
+    _, idx = ops.select_frames(ts, offs, q, perm=perm, song_level=sl)
     return _positions(idx), uniq
 
 

@@ -49,26 +49,49 @@ import numpy as np
 import torch
 
 from . import ops
-from .select import MODES, _device, _hc_tensor, song_groups, stack_committee
+from .select import MODES, _device, _hc_tensor, frame_member_tensors, groupby_device, stack_committee
 
 
-def frame_member_tensors(frames, n_songs, n_frames, grouped, dev):
-    """Members handed to a session as ``frames=``: device tensors and their
-    song-level flags by committee_from_frames' rule -- [F, C] rows in X_train
-    order are frame-level, [N, C] rows song-level (F == N with the frames
-    already grouped: song-level, each song being its one frame)."""
-    ts, sl = [], []
-    for m, a in enumerate(frames):
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(getattr(a, "values", a)))
-        if t.dtype not in (torch.float32, torch.float64):
-            t = t.to(torch.float64)
-        if t.dim() != 2 or t.shape[0] not in (n_frames, n_songs):
-            raise ValueError(f"member {m} has shape {tuple(t.shape)}: neither {n_frames} frames nor {n_songs} songs")
-        ts.append(t.to(dev))
-        sl.append(not (t.shape[0] == n_frames and (n_frames != n_songs or not grouped)))
-    if not ts:
-        raise ValueError("committee has no members")
-    return ts, sl
+def twin_maps(hc_to_mc, offsets, hc_offsets, pool="N_u"):
+    """The mix twin maps of U users, on the host.  ``hc_to_mc``: per hc row the
+    user-local committee item of the same song or -1 (None: the identity, only
+    when the pools coincide); ``offsets`` / ``hc_offsets``: int64 [U + 1].
+    Returns (h2m local [total_h], h2m global [total_h], m2h global
+    [total_items]), global = stacked indices, -1 = no twin.  ``pool`` names a
+    user's pool size in the range error."""
+    n_items, total_h = np.diff(offsets), int(hc_offsets[-1])
+    if hc_to_mc is None:
+        if not np.array_equal(hc_offsets, offsets):
+            raise ValueError("mix: pass hc_to_mc (user-local committee item of each hc row) when the hc pools "
+                             "(hc_offsets) differ from the committee pools (offsets)")
+        h2m = np.concatenate([np.arange(n) for n in n_items] + [np.zeros(0, np.int64)])
+    else:
+        h2m = np.asarray(hc_to_mc, dtype=np.int64).reshape(-1)
+    if h2m.shape[0] != total_h:
+        raise ValueError(f"hc_to_mc must hold one entry per hc row ({total_h})")
+    h2m_g = np.full(total_h, -1, np.int64)
+    m2h_g = np.full(int(offsets[-1]), -1, np.int64)
+    for u in range(len(n_items)):
+        rows = np.arange(hc_offsets[u], hc_offsets[u + 1])
+        loc = h2m[rows]
+        if (loc >= n_items[u]).any() or (loc < -1).any():
+            raise ValueError(f"hc_to_mc must give, per hc row, a committee item in [0, {pool}) or -1 (user {u})")
+        ok = loc >= 0
+        if len(np.unique(loc[ok])) != ok.sum():
+            raise ValueError(f"hc_to_mc maps two hc rows to one committee item (user {u})")
+        h2m_g[rows[ok]] = offsets[u] + loc[ok]
+        m2h_g[offsets[u] + loc[ok]] = rows[ok]
+    return h2m, h2m_g, m2h_g
+
+
+def songs_leaving(picks, n_items, h2m_rows):
+    """Songs that leave a user's committee pool after a mix epoch.  ``picks``:
+    the user's picked positions (>= 0; i < n_items a committee item, n_items + j
+    hc row j); ``h2m_rows``: the user's local hc_to_mc.  A pick through either
+    part counts, a song picked through both once, and an hc pick of a song
+    outside the pool (twin -1) leaves only the table."""
+    via_hc = h2m_rows[picks[picks >= n_items] - n_items]
+    return len(np.unique(np.concatenate([picks[picks < n_items], via_hc[via_hc >= 0]])))
 
 
 class SelectionSession:
@@ -81,19 +104,15 @@ class SelectionSession:
             raise ValueError(f"queries = {self.q} is negative")
         self.mode = mode
         self.N = int(n_items)
-        # frame-level members (select(frames=...)): the groupby geometry of the
-        # FULL X_train, computed once; checked on the host before any device work
+        self.dev = _device(device)
+        # frame-level members (select(frames=...)): the groupby geometry of the FULL X_train, on the device once
         self.song_ids = None
-        geom = None
         if s_id is not None:
             if mode in ("hc", "rand"):
                 raise ValueError(f"s_id (frame-level members) has no use in mode {mode!r}: it selects from no committee")
-            geom = song_groups(s_id)
-            if len(geom[0]) != self.N:
-                raise ValueError(f"s_id names {len(geom[0])} songs, n_items is {self.N}")
-            self.song_ids = geom[0]
-            self._F = int(geom[1][-1])
-        self.dev = _device(device)
+            self.song_ids, n, self._F, self._f_off, self._f_perm = groupby_device(s_id, self.dev)
+            if n != self.N:
+                raise ValueError(f"s_id names {n} songs, n_items is {self.N}")
         self.rng = rng
         self.H = None
         if mode in ("hc", "mix"):
@@ -102,9 +121,7 @@ class SelectionSession:
                 self.N = self.H.shape[0]
         self.excl = ops.excl_bitmap(self.N, self.dev)
         self.n_selected = 0
-        if geom is not None:
-            self._f_off = torch.from_numpy(geom[1]).to(self.dev)
-            self._f_perm = torch.from_numpy(geom[2]).to(self.dev) if geom[2] is not None else None
+        if self.song_ids is not None:
             # mix: the consensus rows of the remaining songs, a one-member committee for the mix path
             self._cons = (torch.zeros((self.N, self.H.shape[1]), dtype=torch.float64, device=self.dev)
                           if mode == "mix" else None)
@@ -115,23 +132,12 @@ class SelectionSession:
                 raise ValueError("rand_order must be a permutation of the n_items pool positions")
             self.rand_order = order
         if mode == "mix":
-            Nh = self.H.shape[0]
-            if hc_to_mc is None:
-                if Nh != self.N:
-                    raise ValueError("mix: pass hc_to_mc (committee item of each hc row) when the pools differ")
-                hc_to_mc = np.arange(Nh)
-            h2m = np.asarray(hc_to_mc, dtype=np.int64).reshape(-1)
-            if h2m.shape[0] != Nh or (h2m >= self.N).any() or (h2m < -1).any():
-                raise ValueError("hc_to_mc must give, per hc row, a committee item in [0, n_items) or -1")
-            valid = h2m[h2m >= 0]
-            if len(np.unique(valid)) != len(valid):
-                raise ValueError("hc_to_mc maps two hc rows to one committee item")
-            m2h = np.full(self.N, -1, np.int64)
-            m2h[valid] = np.flatnonzero(h2m >= 0)
+            self.Nh = self.H.shape[0]
+            # one user: the global maps are the local ones; the host copy counts the songs leaving the pool
+            self._h2m_host, h2m, m2h = twin_maps(hc_to_mc, np.array([0, self.N]), np.array([0, self.Nh]), "n_items")
             self.h2m = torch.from_numpy(h2m).to(self.dev)
             self.m2h = torch.from_numpy(m2h).to(self.dev)
-            self.Nh = Nh
-            self.excl_hc = ops.excl_bitmap(Nh, self.dev)
+            self.excl_hc = ops.excl_bitmap(self.Nh, self.dev)
 
     @property
     def remaining(self):
@@ -213,11 +219,7 @@ class SelectionSession:
             ops.mark_selected(self.excl_hc, self.Nh, hrow)
         out = idx.cpu().numpy()
         out = out[out >= 0]
-        if self.mode == "mix":
-            # songs leaving the committee pool (an hc pick of a song outside it leaves only the table)
-            self.n_selected += len(np.unique(song.cpu().numpy()[song.cpu().numpy() >= 0]))
-        else:
-            self.n_selected += len(out)
+        self.n_selected += songs_leaving(out, self.N, self._h2m_host) if self.mode == "mix" else len(out)
         return out
 
     def _mask(self):

@@ -328,3 +328,79 @@ def test_bench_spawn_ranks_env_and_status(tmp_path):
         del os.environ["FAIL_RANK"]
     kill = "import os, signal; os.kill(os.getpid(), signal.SIGKILL) if os.environ['RANK'] == '0' else None"
     assert bench.spawn_ranks([sys.executable, "-c", kill], 2, poll_s=0.05) == 128 + 9
+
+
+def test_frame_member_rule_table_without_gpu():
+    """amg_test.py:430-437 as every frames entry point reads it (one function):
+    [F, C] rows are frame-level and [N, C] rows song-level; with F == N the
+    rows are song-level iff the frames are already grouped."""
+    torch = pytest.importorskip("torch")
+    from ce_amd.select import frame_member_tensors, groupby_device
+
+    C = 4
+    for s_id, expect in (([0, 0, 0, 1, 1, 2, 2], {7: False, 3: True}),   # F = 7 grouped
+                         ([2, 0, 1, 0, 2, 1, 0], {7: False, 3: True}),   # F = 7 shuffled
+                         ([0, 1, 2], {3: True}),                         # F = N grouped: each song is its one frame
+                         ([2, 0, 1], {3: False})):                       # F = N shuffled: rows in X_train order
+        uniq, N, F, offs, perm = groupby_device(np.array(s_id) * 5 + 1, "cpu")
+        assert (uniq.tolist(), N, F) == ([1, 6, 11], 3, len(s_id))
+        assert offs.dtype == torch.int64 and offs.tolist()[0] == 0 and offs.tolist()[-1] == F
+        assert (perm is None) == (s_id == sorted(s_id))
+        for rows, song_level in expect.items():
+            members = [np.full((rows, C), 0.25), torch.full((rows, C), 0.25, dtype=torch.float32),
+                       np.ones((rows, C), dtype=np.int32)]
+            ts, sl = frame_member_tensors(members, N, F, perm is None, "cpu")
+            assert sl == [song_level] * 3, (s_id, rows)
+            assert [t.dtype for t in ts] == [torch.float64, torch.float32, torch.float64]  # others through float64
+        with pytest.raises(ValueError, match="neither"):
+            frame_member_tensors([np.zeros((F, C)), np.zeros((5, C))], N, F, perm is None, "cpu")
+        with pytest.raises(ValueError, match="neither"):
+            frame_member_tensors([np.zeros(F)], N, F, perm is None, "cpu")
+        with pytest.raises(ValueError, match="no members"):
+            frame_member_tensors([], N, F, perm is None, "cpu")
+
+
+def test_twin_maps_without_gpu():
+    """The mix twin maps against maps written out by hand: one user (global =
+    local), three users with an empty one and a -1, the identity default and
+    the three refusals."""
+    pytest.importorskip("torch")
+    from ce_amd.session import twin_maps
+
+    i64 = lambda *a: np.array(a, dtype=np.int64)
+    loc, h2m, m2h = twin_maps([2, -1, 0], i64(0, 4), i64(0, 3), "n_items")  # N = 4, Nh = 3
+    assert loc.tolist() == h2m.tolist() == [2, -1, 0] and m2h.tolist() == [2, -1, 0, -1]
+    assert loc.dtype == h2m.dtype == m2h.dtype == np.int64
+    # users of 3, 0 and 2 items with 2, 0 and 3 hc rows
+    off, off_h = i64(0, 3, 3, 5), i64(0, 2, 2, 5)
+    loc, h2m, m2h = twin_maps([1, -1, 1, 0, -1], off, off_h)
+    assert loc.tolist() == [1, -1, 1, 0, -1]
+    assert h2m.tolist() == [1, -1, 4, 3, -1] and m2h.tolist() == [-1, 0, -1, 3, 2]
+    # the identity default, only when the pools coincide
+    loc, h2m, m2h = twin_maps(None, i64(0, 2, 2, 5), i64(0, 2, 2, 5))
+    assert loc.tolist() == [0, 1, 0, 1, 2] and h2m.tolist() == m2h.tolist() == [0, 1, 2, 3, 4]
+    with pytest.raises(ValueError, match="hc_to_mc"):
+        twin_maps(None, off, off_h)
+    with pytest.raises(ValueError, match=r"\[0, N_u\).*user 2"):
+        twin_maps([1, -1, 2, 0, -1], off, off_h)  # user 2 has items 0..1
+    with pytest.raises(ValueError, match=r"\[0, n_items\)"):
+        twin_maps([2, -2, 0], i64(0, 4), i64(0, 3), "n_items")
+    with pytest.raises(ValueError, match="two hc rows.*user 2"):
+        twin_maps([0, -1, 0, 0, -1], off, off_h)  # item 0 in two users is fine; twice in user 2 is not
+    with pytest.raises(ValueError, match="hc_to_mc"):
+        twin_maps([1, -1, 1, 0], off, off_h)  # one entry per hc row
+
+
+def test_songs_leaving_without_gpu():
+    """Songs leaving the committee pool after a mix epoch: a song picked through
+    both parts counts once, an hc pick without a twin counts zero."""
+    pytest.importorskip("torch")
+    from ce_amd.session import songs_leaving
+
+    h2m = np.array([2, -1, 0], dtype=np.int64)  # N = 4 items, 3 hc rows
+    picks = lambda *a: np.array(a, dtype=np.int64)
+    assert songs_leaving(picks(2, 4), 4, h2m) == 1      # item 2 and hc row 0, its twin
+    assert songs_leaving(picks(5), 4, h2m) == 0         # hc row 1: the song is not in the pool
+    assert songs_leaving(picks(), 4, h2m) == 0
+    assert songs_leaving(picks(6, 1, 3, 5), 4, h2m) == 3  # hc row 2 -> item 0, items 1 and 3, a twin-less row
+    assert songs_leaving(picks(0, 1), 4, h2m[:0]) == 2  # no hc rows at all
