@@ -48,7 +48,7 @@ import torch
 
 from . import ops
 from .select import MODES, _device, _hc_tensor, frame_member_tensors, stack_committee
-from .session import songs_leaving, twin_maps
+from .session import mix_songs, songs_leaving, twin_maps
 
 _MIX_KERNEL_MAX_Q = 64  # include/ce.h: ce_select_batched_mix runs C = 4, q <= 64
 
@@ -222,6 +222,43 @@ class BatchedSelectionSession:
                                                    self._h2m_local[self._off_h[u]:self._off_h[u + 1]])
             else:
                 self.remaining[u] -= len(r)
+        return out
+
+    def frame_geometry(self):
+        """(frame_offsets [total_items + 1], frame_perm [F] or None, offsets
+        [U + 1]) on the device: stacked song g owns the rows
+        frame_perm[frame_offsets[g]:frame_offsets[g+1]], user u the stacked songs
+        offsets[u]:offsets[u+1] (a session built with ``frame_offsets``)."""
+        if self.frame_offsets is None:
+            raise ValueError("this session was built without frame_offsets: it holds no frame geometry")
+        return self.frame_offsets, self.frame_perm, self.offsets
+
+    def songs_of(self, picks):
+        """The committee song positions (user-local) behind an epoch's picks,
+        i.e. every user's q_songs at amg_test.py:491: in mc mode the picks
+        themselves; in mix mode an hc pick N_u + j goes through hc_to_mc and -1
+        twins are dropped (session.mix_songs).  ``picks``: the list of U arrays
+        ``select`` / ``account`` return -> a list of U int64 arrays, duplicates
+        merged; or the device tensor [U, slots] of ``step`` -> a device tensor
+        of that shape, -1 where a slot names no song (nothing is read back; a
+        song picked through both parts stands twice, ops.batch_rows merges it)."""
+        if self.mode == "hc":
+            raise ValueError("mode 'hc' selects from no committee: its picks name no committee songs")
+        if isinstance(picks, torch.Tensor):
+            if self.mode == "mc":
+                return picks
+            n, lo = self._n_dev, self.offsets[:-1].unsqueeze(1)
+            row = (self.hc_offsets[:-1].unsqueeze(1) + picks - n).clamp(0, max(self.H.shape[0] - 1, 0))
+            twin = self.h2m[row] if self.H.shape[0] else torch.full_like(picks, -1)
+            via_hc = torch.where(twin >= 0, twin - lo, twin)
+            return torch.where(picks < 0, picks, torch.where(picks < n, picks, via_hc))
+        if len(picks) != self.U:
+            raise ValueError(f"picks must hold one array per user ({self.U})")
+        out = []
+        for u, r in enumerate(picks):
+            r = np.asarray(r, dtype=np.int64).reshape(-1)
+            out.append(mix_songs(r, self.n_items[u], self._h2m_local[self._off_h[u]:self._off_h[u + 1]])
+                       if self.mode == "mix" else r[r >= 0])
         return out
 
     def select(self, committee=None, layout="MNC", *, frames=None, _compose=False):

@@ -550,6 +550,144 @@ def sgd_predict_proba(X, coef, intercept, out=None):
     return out
 
 
+def _fit_state(t, what, shape=None):
+    """A tensor the partial_fit updates in place: float64, contiguous, on the device (no copy may stand in)."""
+    _on_gpu(t, what)
+    if t.dtype != torch.float64 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+        want = f" of shape {list(shape)}" if shape is not None else ""
+        raise ValueError(f"{what} must be a contiguous float64 tensor{want} (it is updated in place)")
+    return t
+
+
+def gnb_partial_fit(X, rows, labels, theta, var, class_count, row_offsets=None, var_smoothing=1e-9, *,
+                    class_prior=None, epsilon=None):
+    """GaussianNB.partial_fit on the device (ce_gnb_partial_fit; amg_test.py:509,
+    mod.partial_fit(X_batch.values, y_batch_enc)) for U fitted models at once.
+    X [F, D] f64 frames; model u's batch is the rows ``rows[row_offsets[u]:
+    row_offsets[u+1]]`` of X, row i of class ``labels[i]`` in [0, C), in
+    X_train's order (ascending; ``batch_rows`` builds them from picked songs).
+    theta / var [U, C, D] and class_count [U, C] (or [C, D], [C, D], [C] for one
+    model) are float64 device tensors UPDATED IN PLACE; row_offsets=None means
+    one model owning every row (built on the device: capturable).  Returns
+    (class_prior [U, C], epsilon [U]) -- into ``class_prior`` / ``epsilon``
+    when given; a model with an empty batch is left untouched, these two slots
+    included (NaN in fresh outputs), and with no row at all nothing is launched.
+    Bit-identical to sklearn's update; D = 1 is refused."""
+    F, D = _check_X(X)
+    rows = _i64(rows, "rows").reshape(-1)
+    _on_gpu(labels, "labels")
+    labels = labels.reshape(-1).to(torch.int32).contiguous()
+    if labels.numel() != rows.numel():
+        raise ValueError(f"labels must hold one class per row ({rows.numel()}), got {labels.numel()}")
+    one = theta.dim() == 2 if isinstance(theta, torch.Tensor) else False
+    _fit_state(theta, "theta")
+    if theta.dim() not in (2, 3) or theta.shape[-1] != D:
+        raise ValueError(f"theta must be [U, C, {D}] (or [C, {D}] for one model)")
+    U, C = (1, theta.shape[0]) if one else tuple(theta.shape[:2])
+    _fit_state(var, "var", tuple(theta.shape))
+    _fit_state(class_count, "class_count", tuple(theta.shape[:-1]))
+    if row_offsets is None:
+        if U != 1:
+            raise ValueError(f"{U} models need row_offsets [U + 1]")
+        # [0, n] by two device kernels: no host-to-device copy, so the call stays capturable
+        row_offsets = torch.arange(2, dtype=torch.int64, device=X.device) * rows.numel()
+    row_offsets = _i64(row_offsets, "row_offsets").reshape(-1)
+    if row_offsets.numel() != U + 1:
+        raise ValueError(f"row_offsets must hold U + 1 = {U + 1} entries")
+    lead = tuple(theta.shape[:-2])
+    if class_prior is None:
+        class_prior = torch.full(lead + (C,), math.nan, dtype=torch.float64, device=X.device)
+    if epsilon is None:
+        epsilon = torch.full(lead or (1,), math.nan, dtype=torch.float64, device=X.device)
+    _fit_state(class_prior, "class_prior", tuple(theta.shape[:-1]))
+    _fit_state(epsilon, "epsilon")
+    if epsilon.numel() != U:
+        raise ValueError(f"epsilon must hold one value per model ({U})")
+    if rows.numel() == 0:  # every batch is empty (an epoch that picked nothing): every model stays as it is
+        return class_prior, epsilon
+    call("ce_gnb_partial_fit", _p(X), F, D, X.stride(0), _p(rows), _p(labels), _p(row_offsets), U, C,
+         float(var_smoothing), _p(theta), _p(var), _p(class_count), _p(class_prior), _p(epsilon), _stream(X.device))
+    return class_prior, epsilon
+
+
+def batch_rows(songs, frame_offsets, frame_perm=None, song_labels=None, item_offsets=None, n_classes=None):
+    """From picked songs to X_batch's rows -- amg_test.py:491,
+    ``X_train[X_train.index.isin(q_songs)]``, for one user or U: the frame rows
+    of the picked songs in X_train's order (ascending row, not pick order), a
+    song picked twice taken once.  ``songs``: picked song positions [q], or
+    [U, q] with -1 padding (every -1 is dropped); with ``item_offsets`` [U + 1]
+    they are user-local and user u's song s is stacked song item_offsets[u] + s.
+    A position outside the user's pool is an error when ``songs`` arrives from
+    the host (with host or no ``item_offsets``); on the device it is dropped
+    like -1, never mapped onto another user's song.
+    Song g owns the rows frame_perm[frame_offsets[g]:frame_offsets[g+1]] (or
+    that range itself): the CSR the sessions keep.  ``song_labels``: the class
+    of every (stacked) song; from the host it is checked against [0, n_classes).
+    Returns (rows int64 [R], labels int32 [R], row_offsets int64 [U + 1]), each
+    user's rows ascending, on frame_offsets' device -- torch ops only, so CPU
+    tensors work too; R is the one size read back from the device
+    (repeat_interleave), everything else is sorts, scans and scatters."""
+    if not isinstance(frame_offsets, torch.Tensor):
+        frame_offsets = torch.as_tensor(np.asarray(frame_offsets, dtype=np.int64))
+    dev = frame_offsets.device
+    off = frame_offsets.to(torch.int64).reshape(-1)
+    n_songs = off.numel() - 1
+
+    def idx(t):
+        return None if t is None else torch.as_tensor(t).to(device=dev, dtype=torch.int64)
+
+    if song_labels is None:
+        raise ValueError("batch_rows needs song_labels, the class of every song")
+    if not isinstance(song_labels, torch.Tensor):
+        host = np.asarray(getattr(song_labels, "values", song_labels))
+        if n_classes is not None and host.size and (host.min() < 0 or host.max() >= n_classes):
+            raise ValueError(f"song_labels must lie in [0, {n_classes})")
+        song_labels = torch.from_numpy(np.ascontiguousarray(host).astype(np.int64))
+    lab = song_labels.to(device=dev, dtype=torch.int64).reshape(-1)
+    if lab.numel() != n_songs:
+        raise ValueError(f"song_labels must hold one class per song ({n_songs}), got {lab.numel()}")
+    if not isinstance(songs, torch.Tensor) and not isinstance(item_offsets, torch.Tensor):  # host picks: check them
+        hs = np.asarray(songs, dtype=np.int64)
+        hs = hs.reshape(1, -1) if hs.ndim < 2 else hs.reshape(hs.shape[0], -1)
+        pool = (np.full(hs.shape[0], n_songs) if item_offsets is None
+                else np.diff(np.asarray(item_offsets, dtype=np.int64).reshape(-1))[:hs.shape[0]])
+        if len(pool) == hs.shape[0] and ((hs < -1) | (hs >= pool[:, None])).any():
+            raise ValueError("songs must be positions in the user's pool, or -1")
+    S = idx(songs)
+    S = S.reshape(1, -1) if S.dim() < 2 else S.reshape(S.shape[0], -1)
+    U = S.shape[0]
+    row_offsets = torch.zeros(U + 1, dtype=torch.int64, device=dev)
+    if item_offsets is not None:
+        io = idx(item_offsets).reshape(-1)
+        if io.numel() != U + 1:
+            raise ValueError(f"item_offsets must hold U + 1 = {U + 1} entries")
+        G, pool = S + io[:-1].unsqueeze(1), (io[1:] - io[:-1]).unsqueeze(1)
+    else:
+        G, pool = S, n_songs
+    if n_songs == 0 or S.numel() == 0:
+        return S.new_zeros(0), torch.zeros(0, dtype=torch.int32, device=dev), row_offsets
+    # (user, song) keys in user-then-song order; a slot that names no song gets the key past every user
+    user = torch.arange(U, device=dev).unsqueeze(1)
+    valid = (S >= 0) & (S < pool) & (G < n_songs)
+    key, _ = torch.sort(torch.where(valid, user * n_songs + G, U * n_songs).reshape(-1))
+    first = key < U * n_songs  # the first slot of every key: a song picked twice is taken once
+    first[1:] &= key[1:] != key[:-1]
+    uu, g = (key // n_songs).clamp(max=U - 1), key % n_songs
+    cnt = torch.where(first, off[g + 1] - off[g], 0)
+    seg = torch.repeat_interleave(torch.arange(key.numel(), device=dev), cnt)  # the one size read-back
+    start = torch.cumsum(cnt, 0) - cnt
+    rows = off[g][seg] + (torch.arange(seg.numel(), device=dev) - start[seg])
+    ruser, rlab = uu[seg], lab[g][seg]
+    if frame_perm is not None:  # permuted frames: a song's rows are scattered, so order each user's rows again
+        rows = idx(frame_perm).reshape(-1)[rows]
+        rows, o = torch.sort(rows, stable=True)
+        ruser, rlab = ruser[o], rlab[o]
+        ruser, o = torch.sort(ruser, stable=True)
+        rows, rlab = rows[o], rlab[o]
+    row_offsets[1:] = torch.cumsum(torch.zeros(U, dtype=torch.int64, device=dev).index_add_(0, uu, cnt), 0)
+    return rows, rlab.to(torch.int32), row_offsets
+
+
 def xgb_predict_proba(X, forest, out=None, out_dtype=torch.float32):
     """XGBClassifier(...).predict_proba(X) on the device (xgboost 1.3.3
     predictor restated in csrc/ce_xgb.hip; xgboost/sklearn.py:991-1029,

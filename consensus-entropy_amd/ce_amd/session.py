@@ -84,14 +84,23 @@ def twin_maps(hc_to_mc, offsets, hc_offsets, pool="N_u"):
     return h2m, h2m_g, m2h_g
 
 
-def songs_leaving(picks, n_items, h2m_rows):
-    """Songs that leave a user's committee pool after a mix epoch.  ``picks``:
-    the user's picked positions (>= 0; i < n_items a committee item, n_items + j
-    hc row j); ``h2m_rows``: the user's local hc_to_mc.  A pick through either
-    part counts, a song picked through both once, and an hc pick of a song
-    outside the pool (twin -1) leaves only the table."""
+def mix_songs(picks, n_items, h2m_rows):
+    """The committee songs behind a user's mix picks, stated once (amg_test.py
+    :484 + :491, ``isin(q_songs)``).  ``picks``: the user's picked positions
+    (>= 0; i < n_items a committee item, n_items + j hc row j); ``h2m_rows``: the
+    user's local hc_to_mc.  A pick through either part counts, a song picked
+    through both once, and an hc pick of a song outside the pool (twin -1) names
+    no committee song.  Returns the sorted unique positions."""
+    picks = np.asarray(picks, dtype=np.int64).reshape(-1)
+    picks = picks[picks >= 0]
     via_hc = h2m_rows[picks[picks >= n_items] - n_items]
-    return len(np.unique(np.concatenate([picks[picks < n_items], via_hc[via_hc >= 0]])))
+    return np.unique(np.concatenate([picks[picks < n_items], via_hc[via_hc >= 0]]))
+
+
+def songs_leaving(picks, n_items, h2m_rows):
+    """Songs that leave a user's committee pool after a mix epoch: mix_songs,
+    counted (an hc pick whose twin is -1 leaves only the table)."""
+    return len(mix_songs(picks, n_items, h2m_rows))
 
 
 class SelectionSession:
@@ -221,6 +230,27 @@ class SelectionSession:
         out = out[out >= 0]
         self.n_selected += songs_leaving(out, self.N, self._h2m_host) if self.mode == "mix" else len(out)
         return out
+
+    def frame_geometry(self):
+        """(frame_offsets [N + 1], frame_perm [F] or None, None) on the device:
+        song n owns the rows frame_perm[frame_offsets[n]:frame_offsets[n+1]] of
+        the full X_train (a session built with ``s_id``); the last entry is the
+        users' item offsets, None for one user (BatchedSelectionSession has them)."""
+        if self.song_ids is None:
+            raise ValueError("this session was built without s_id: it holds no frame geometry")
+        return self._f_off, self._f_perm, None
+
+    def songs_of(self, picks):
+        """The committee song positions behind an epoch's picks (np.int64), i.e.
+        the q_songs that X_train.index.isin selects at amg_test.py:491: in mc
+        mode the picks themselves; in mix mode an hc pick N + j goes through
+        hc_to_mc, -1 twins are dropped and duplicates merged (mix_songs)."""
+        if self.mode in ("hc", "rand"):
+            raise ValueError(f"mode {self.mode!r} selects from no committee: its picks name no committee songs")
+        picks = np.asarray(picks.cpu() if isinstance(picks, torch.Tensor) else picks, dtype=np.int64).reshape(-1)
+        if self.mode == "mix":
+            return mix_songs(picks, self.N, self._h2m_host)
+        return picks[picks >= 0]
 
     def _mask(self):
         """The exclusion bitmap as a host bool array [N] (True = queried)."""

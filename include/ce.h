@@ -210,6 +210,44 @@ int ce_sgd_predict_proba(const double *X, int64_t F, int32_t D, int64_t ld, cons
                          ce_stream_t stream);
 
 /*
+ * GaussianNB.partial_fit on the device -- replaces
+ * amg_test.py:509, mod.partial_fit(X_batch.values, y_batch_enc), the retrain
+ * step of an epoch, for U already-fitted models (priors=None) in one launch,
+ * one workgroup per model.  Model u's batch is the rows
+ * rows[row_offsets[u] .. row_offsets[u+1]) of X [F, D] f64 (row stride ld),
+ * row i of class labels[i]; theta / var [U, C, D] and class_count [U, C] are
+ * updated IN PLACE, class_prior [U, C] and epsilon [U] are written.  sklearn's
+ * steps, operation for operation (read from sklearn 1.7.2; parity with the
+ * reference's pinned 0.24.1, where var_ is sigma_, is unpinned):
+ *   1. epsilon = var_smoothing * np.var(X_batch, axis=0).max(), over the whole
+ *      batch (NaN if any cell of it is);
+ *   2. var -= epsilon (the NEW batch's epsilon, as sklearn does);
+ *   3. per class c in the batch, new_mu = np.mean(X_c, 0), new_var =
+ *      np.var(X_c, 0) (rows summed one after the other in the order given,
+ *      onto +0.0; true divides, no FMA): taken as they are when
+ *      class_count[c] == 0, else merged (_update_mean_variance):
+ *        total_mu  = (n_new * new_mu + n_past * mu) / n_total
+ *        total_var = ((n_past * var + n_new * new_var)
+ *                     + (n_new * n_past / n_total) * (mu - new_mu)**2) / n_total
+ *      and class_count[c] += n_new; a class absent from the batch keeps theta
+ *      and class_count, its var still goes through - epsilon + epsilon;
+ *   4. var += epsilon;
+ *   5. class_prior = class_count / class_count.sum() (whole numbers: exact in any order).
+ * Bit-identical to sklearn for 2 <= D <= 512 and 2 <= C <= 8; D = 1 is
+ * CE_EUNSUPPORTED (numpy sums a single column pairwise, not row by row).
+ * A model with an empty batch is left untouched, its epsilon and class_prior
+ * slots included.  Preconditions (not checked on the device): every row in
+ * [0, F), every label in [0, C), and the rows of a batch in the order of
+ * X_train (ascending frame row: X_train[X_train.index.isin(q_songs)], :491) --
+ * the sums follow the order given.  rows, labels, row_offsets [U + 1]: DEVICE
+ * memory.  No workspace, no allocation; stream-ordered and capturable.
+ */
+int ce_gnb_partial_fit(const double *X, int64_t F, int32_t D, int64_t ld, const int64_t *rows,
+                       const int32_t *labels, const int64_t *row_offsets, int32_t U, int32_t C,
+                       double var_smoothing, double *theta, double *var, double *class_count,
+                       double *class_prior, double *epsilon, ce_stream_t stream);
+
+/*
  * XGBClassifier.predict_proba on the device (the
  * 'classifier_xgb' member; amg_test.py:435/:467 -> xgboost/sklearn.py:991-1029
  * -> libxgboost 1.3.3 CPU predictor, restated in csrc/ce_xgb.hip).
