@@ -39,6 +39,9 @@ SIGNATURES = {
     "ce_sgd_predict_proba": (_int, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
     "ce_gnb_partial_fit": (_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _i32, ctypes.c_double, _vp, _vp, _vp, _vp,
                                   _vp, _vp]),
+    "ce_sgd_partial_fit_workspace_bytes": (_sz, [_i64, _i32]),
+    "ce_sgd_partial_fit": (_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _i32, ctypes.c_double, ctypes.c_double,
+                                  _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ce_xgb_predict_proba": (_int, [_vp, _int, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _i32, ctypes.c_float, _i32,
                                     _vp, _int, _i64, _vp]),
     "ce_xgb_lane_table": (_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),

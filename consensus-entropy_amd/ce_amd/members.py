@@ -7,7 +7,9 @@ GaussianNB members (one per user) on the device and closes the loop there:
 ops.gnb_partial_fit -- sklearn's ``mod.partial_fit(X_batch, y_batch)`` of :509,
 bit for bit -- and ``partial_fit_picks`` goes from a session's picks to the
 batch (``X_train[X_train.index.isin(q_songs)]``, :491) without the host
-gathering a frame.
+gathering a frame.  ``DeviceSGDClassifier`` is the same for the other member
+type :509 retrains, 'classifier_sgd' (ops.sgd_predict_proba,
+ops.sgd_partial_fit).
 """
 from __future__ import annotations
 
@@ -16,6 +18,36 @@ import torch
 
 from . import ops
 from .select import _device
+
+
+def _own_f64(a, dev):
+    """A private float64 copy on the device: the updates are in place."""
+    if isinstance(a, torch.Tensor):
+        t = a.detach().to(device=dev, dtype=torch.float64, copy=True)
+    else:
+        t = torch.from_numpy(np.array(a, dtype=np.float64)).to(dev)
+    return t.contiguous()
+
+
+def _picks_batch(session, picks, song_labels, U, C, dev):
+    """From a session's picks to the batch every model retrains on
+    (amg_test.py:484-491): the picks become committee songs
+    (``session.songs_of``), the songs the frame rows of X_batch through the
+    session's own frame geometry (ops.batch_rows).  Returns (rows, labels,
+    row_offsets) for the U models of a member with C classes."""
+    f_off, f_perm, items = session.frame_geometry()
+    users = 1 if items is None else items.numel() - 1
+    if users != U:
+        raise ValueError(f"the session has {users} user(s), this member {U} model(s)")
+    songs = session.songs_of(picks)
+    if isinstance(songs, list):  # one array per user: pad to [U, width] with -1
+        pad = np.full((U, max([len(s) for s in songs] + [1])), -1, np.int64)
+        for u, s in enumerate(songs):
+            pad[u, :len(s)] = s
+        songs = pad
+    if not isinstance(songs, torch.Tensor):
+        songs = torch.from_numpy(np.ascontiguousarray(songs, dtype=np.int64)).to(dev)
+    return ops.batch_rows(songs, f_off, f_perm, song_labels=song_labels, item_offsets=items, n_classes=C)
 
 
 class DeviceGaussianNB:
@@ -27,12 +59,8 @@ class DeviceGaussianNB:
     def __init__(self, theta, var, class_count, class_prior=None, var_smoothing=1e-9, device=None):
         self.dev = _device(device)
 
-        def own(a):  # a private float64 copy: the updates are in place
-            if isinstance(a, torch.Tensor):
-                t = a.detach().to(device=self.dev, dtype=torch.float64, copy=True)
-            else:
-                t = torch.from_numpy(np.array(a, dtype=np.float64)).to(self.dev)
-            return t.contiguous()
+        def own(a):
+            return _own_f64(a, self.dev)
 
         theta = own(theta)
         if theta.dim() == 2:
@@ -74,23 +102,96 @@ class DeviceGaussianNB:
         class of every song of the (stacked) pool, in [0, C).  An epoch that
         picked nothing (a dry pool, only -1, only hc picks without a twin)
         leaves the models, class_prior and epsilon as they are."""
-        f_off, f_perm, items = session.frame_geometry()
-        users = 1 if items is None else items.numel() - 1
-        if users != self.U:
-            raise ValueError(f"the session has {users} user(s), this member {self.U} model(s)")
-        songs = session.songs_of(picks)
-        if isinstance(songs, list):  # one array per user: pad to [U, width] with -1
-            pad = np.full((self.U, max([len(s) for s in songs] + [1])), -1, np.int64)
-            for u, s in enumerate(songs):
-                pad[u, :len(s)] = s
-            songs = pad
-        if not isinstance(songs, torch.Tensor):
-            songs = torch.from_numpy(np.ascontiguousarray(songs, dtype=np.int64)).to(self.dev)
-        rows, labels, row_offsets = ops.batch_rows(songs, f_off, f_perm, song_labels=song_labels, item_offsets=items,
-                                                   n_classes=self.C)
+        rows, labels, row_offsets = _picks_batch(session, picks, song_labels, self.U, self.C, self.dev)
         return self.partial_fit(X, rows, labels, row_offsets)
 
     def state(self):
         """Host copies: dict of theta [U, C, D], var, class_count [U, C], class_prior, epsilon [U]."""
         return {k: getattr(self, k).cpu().numpy().copy()
                 for k in ("theta", "var", "class_count", "class_prior", "epsilon")}
+
+
+SGD_OVERFLOW = ("Floating-point under-/overflow occurred at epoch #1. Scaling input data with StandardScaler or "
+                "MinMaxScaler might help.")  # sklearn's text (_plain_sgd)
+
+
+class DeviceSGDClassifier:
+    """U SGDClassifier(loss='log', penalty='l2', learning_rate='optimal')
+    models on the device: the reference's 'classifier_sgd' member
+    (deam_classifier.py:214-217).  coef [U, K, D] (coef_), intercept [U, K]
+    (intercept_), t [U] (t_: 1.0 for a model that has seen no row); [K, D],
+    [K] and a number mean U = 1.  K = C one-vs-rest problems, or 1 for C = 2.
+    ``random_state``: the integer the model was built with (one for all, or one
+    per model) -- the shuffle seeds follow from it (ops.sgd_chain_seeds) and are
+    the same for every partial_fit.  ``grad``: "half_binomial" (sklearn >= 1.x,
+    bit-identical to 1.7.2) or "log_dloss" (sklearn 0.24.1's gradient; unpinned)."""
+
+    def __init__(self, coef, intercept, t, alpha=1e-4, random_state=None, grad="half_binomial", device=None):
+        self.dev = _device(device)
+        coef = _own_f64(coef, self.dev)
+        if coef.dim() == 1:
+            coef = coef.unsqueeze(0)
+        if coef.dim() == 2:
+            coef = coef.unsqueeze(0)
+        if coef.dim() != 3:
+            raise ValueError("coef must be [U, K, D] or [K, D]")
+        self.U, self.K, self.D = coef.shape
+        if not 1 <= self.K <= 8 or self.K == 2:
+            raise ValueError(f"coef holds K = {self.K} binary problems: K = 1 (two classes) or 3 .. 8 (one per class)")
+        self.C = 2 if self.K == 1 else self.K
+        self.coef = coef
+        self.intercept = _own_f64(intercept, self.dev).reshape(self.U, self.K)
+        self.t = _own_f64(np.broadcast_to(np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t, np.float64).reshape(-1),
+                                          (self.U,)), self.dev)
+        if random_state is None:
+            raise ValueError("DeviceSGDClassifier needs the integer random_state of the model (None cannot be reproduced)")
+        states = np.asarray(random_state).reshape(-1)
+        if states.size not in (1, self.U):
+            raise ValueError(f"random_state must be one integer or one per model ({self.U})")
+        seeds = np.stack([ops.sgd_chain_seeds(int(r), self.C) for r in np.broadcast_to(states, (self.U,))])
+        self.seeds = torch.from_numpy(seeds.view(np.int32)).to(self.dev)  # [U, K]: on the device once, so a fit is capturable
+        self.status = torch.zeros(self.U, dtype=torch.int32, device=self.dev)
+        self.alpha = float(alpha)
+        ops.sgd_optimal_init(self.alpha)  # refuses a bad alpha here
+        if grad not in ops.SGD_GRADS:
+            raise ValueError(f"grad must be one of {sorted(ops.SGD_GRADS)}, got {grad!r}")
+        self.grad = grad
+
+    def predict_proba(self, X, u=0, out=None):
+        """Model u's predict_proba over the frames X [F, D] (ops.sgd_predict_proba)."""
+        return ops.sgd_predict_proba(X, self.coef[u], self.intercept[u], out=out)
+
+    def partial_fit(self, X, rows, labels, row_offsets=None):
+        """mod.partial_fit(X[rows], labels) for every model, in place: model u
+        takes rows[row_offsets[u]:row_offsets[u+1]] (row_offsets=None: one
+        model, every row), given in X_train's order.  A model with no row is
+        left untouched.  Nothing is read back: ``check_finite`` reports where
+        sklearn would have raised.  Returns self."""
+        ops.sgd_partial_fit(X, rows, labels, self.coef, self.intercept, self.t, row_offsets, self.alpha,
+                            seeds=self.seeds, grad=self.grad, status=self.status)
+        return self
+
+    def partial_fit_picks(self, X, session, picks, song_labels):
+        """The retrain step of an epoch (amg_test.py:491-509) from a session's
+        picks, as DeviceGaussianNB.partial_fit_picks: a SelectionSession built
+        with ``s_id`` (one model) or a BatchedSelectionSession built with
+        ``frame_offsets`` (one model per user).  An epoch that picked nothing
+        leaves the models as they are."""
+        rows, labels, row_offsets = _picks_batch(session, picks, song_labels, self.U, self.C, self.dev)
+        return self.partial_fit(X, rows, labels, row_offsets)
+
+    def check_finite(self):
+        """Reads the models' flags (one device-to-host copy).  Raises sklearn's
+        ValueError where a partial_fit left an intercept or a weight non-finite,
+        a RuntimeError where a model was not run; the flags stay set."""
+        st = self.status.cpu().numpy()
+        if (st == 2).any():
+            raise RuntimeError(f"model(s) {np.flatnonzero(st == 2).tolist()} were not updated: "
+                               "a batch of 2^31 rows or more, or no workspace for its permutations")
+        if (st != 0).any():
+            raise ValueError(f"{SGD_OVERFLOW} (model(s) {np.flatnonzero(st != 0).tolist()})")
+        return self
+
+    def state(self):
+        """Host copies: dict of coef [U, K, D], intercept [U, K], t [U], status [U]."""
+        return {k: getattr(self, k).cpu().numpy().copy() for k in ("coef", "intercept", "t", "status")}

@@ -610,6 +610,121 @@ def gnb_partial_fit(X, rows, labels, theta, var, class_count, row_offsets=None, 
     return class_prior, epsilon
 
 
+SGD_GRADS = {"half_binomial": 0, "log_dloss": 1}  # sklearn >= 1.x (pinned: 1.7.2) / sklearn 0.24.1's Log.dloss
+_INT32_MAX = int(np.iinfo(np.int32).max)
+
+
+def sgd_chain_seeds(random_state, C):
+    """The shuffle seeds of one SGDClassifier.partial_fit call, uint32 [K]
+    (K = C one-vs-rest problems, 1 for C = 2) -- the host rule, numpy's legacy
+    MT19937 as sklearn draws from it.  An integer random_state re-seeds on
+    every call, so the seeds are the same for every call: for C > 2
+    ``RandomState(random_state).randint(INT32_MAX, size=C)`` seeds one
+    RandomState per problem (C = 2: RandomState(random_state) itself); each
+    gives one draw to make_dataset (``randint(1, INT32_MAX)``, discarded) and
+    the next, ``randint(INT32_MAX)``, seeds the shuffle.  random_state=None
+    cannot be reproduced and is refused."""
+    if isinstance(random_state, bool) or not isinstance(random_state, (int, np.integer)):
+        raise ValueError("sgd_chain_seeds needs an integer random_state (None or a generator cannot be reproduced)")
+    if not 2 <= int(C) <= 8:
+        raise ValueError(f"C must be in [2, 8], got {C}")
+    if C > 2:
+        chains = [np.random.RandomState(int(s))
+                  for s in np.random.RandomState(int(random_state)).randint(_INT32_MAX, size=int(C))]
+    else:
+        chains = [np.random.RandomState(int(random_state))]
+    out = []
+    for rs in chains:
+        rs.randint(1, _INT32_MAX)  # make_dataset's draw
+        out.append(rs.randint(_INT32_MAX))
+    return np.array(out, dtype=np.uint32)
+
+
+def sgd_optimal_init(alpha):
+    """learning_rate='optimal': the offset of t in eta = 1 / (alpha * (optimal_init + t - 1)),
+    computed the way _plain_sgd does (the half-binomial gradient at (1, -typw) is negative for every alpha)."""
+    alpha = float(alpha)
+    if not (alpha > 0 and math.isfinite(alpha)):
+        raise ValueError(f"alpha must be positive and finite, got {alpha}")
+    typw = math.sqrt(1.0 / math.sqrt(alpha))
+    p = -typw
+    if p > -37.0:
+        e = math.exp(-p)
+        g = ((1.0 - 1.0) - 1.0 * e) / (1.0 + e)
+    else:
+        g = math.exp(p) - 1.0
+    return 1.0 / ((typw / max(1.0, g)) * alpha)
+
+
+def sgd_partial_fit(X, rows, labels, coef, intercept, t, row_offsets=None, alpha=1e-4, *, seeds,
+                    grad="half_binomial", status=None):
+    """SGDClassifier(loss='log', penalty='l2').partial_fit on the device
+    (ce_sgd_partial_fit; amg_test.py:509 for the 'classifier_sgd' member,
+    deam_classifier.py:214-217) for U models at once.  X [F, D] f64 frames;
+    model u's batch is the rows ``rows[row_offsets[u]:row_offsets[u+1]]`` of X,
+    row i of class ``labels[i]`` in [0, C), in X_train's order (``batch_rows``
+    builds them): the shuffle starts from the order given.  coef [U, K, D],
+    intercept [U, K] and t [U] (or [K, D], [K], [1] for one model; K = C, or 1
+    for C = 2) are float64 device tensors UPDATED IN PLACE; row_offsets=None
+    means one model owning every row.  ``seeds``: the shuffle seeds [U, K] (or
+    [K]): ``sgd_chain_seeds(random_state, C)`` per model, or a device tensor
+    of them (int32; what a captured call needs).  ``grad``: "half_binomial"
+    (sklearn >= 1.x; bit-identical to 1.7.2) or "log_dloss" (sklearn 0.24.1's,
+    unpinned).  Returns ``status`` int32 [U] (zeroed when not given; only ever
+    set): 1 where a model's intercept or a weight is non-finite after the
+    update (sklearn raises there), 2 where a model was not run.  A model with
+    an empty batch is left untouched, its t included, and with no row at all
+    nothing is launched."""
+    F, D = _check_X(X)
+    rows = _i64(rows, "rows").reshape(-1)
+    _on_gpu(labels, "labels")
+    labels = labels.reshape(-1).to(torch.int32).contiguous()
+    if labels.numel() != rows.numel():
+        raise ValueError(f"labels must hold one class per row ({rows.numel()}), got {labels.numel()}")
+    if grad not in SGD_GRADS:
+        raise ValueError(f"grad must be one of {sorted(SGD_GRADS)}, got {grad!r}")
+    one = coef.dim() == 2 if isinstance(coef, torch.Tensor) else False
+    _fit_state(coef, "coef")
+    if coef.dim() not in (2, 3) or coef.shape[-1] != D:
+        raise ValueError(f"coef must be [U, K, {D}] (or [K, {D}] for one model)")
+    U, K = (1, coef.shape[0]) if one else tuple(coef.shape[:2])
+    if not 1 <= K <= 8 or K == 2:
+        raise ValueError(f"coef holds K = {K} binary problems: K = 1 (two classes) or 3 .. 8 (one per class)")
+    C = 2 if K == 1 else K
+    _fit_state(intercept, "intercept", tuple(coef.shape[:-1]))
+    _fit_state(t, "t")
+    if t.numel() != U:
+        raise ValueError(f"t must hold one step count per model ({U})")
+    if row_offsets is None:
+        if U != 1:
+            raise ValueError(f"{U} models need row_offsets [U + 1]")
+        # [0, n] by two device kernels: no host-to-device copy, so the call stays capturable
+        row_offsets = torch.arange(2, dtype=torch.int64, device=X.device) * rows.numel()
+    row_offsets = _i64(row_offsets, "row_offsets").reshape(-1)
+    if row_offsets.numel() != U + 1:
+        raise ValueError(f"row_offsets must hold U + 1 = {U + 1} entries")
+    if not isinstance(seeds, torch.Tensor):  # host seeds (uint32): their bit patterns, as int32
+        seeds = torch.from_numpy(np.ascontiguousarray(seeds).astype(np.uint32).view(np.int32)).to(X.device)
+    _on_gpu(seeds, "seeds")
+    seeds = seeds.to(torch.int32).contiguous()
+    if seeds.numel() != U * K:
+        raise ValueError(f"seeds must hold one shuffle seed per model and problem ({U} x {K})")
+    if status is None:
+        status = torch.zeros(U, dtype=torch.int32, device=X.device)
+    _on_gpu(status, "status")
+    if status.dtype != torch.int32 or not status.is_contiguous() or status.numel() != U:
+        raise ValueError(f"status must be a contiguous int32 tensor of {U} flags")
+    optimal_init = sgd_optimal_init(alpha)
+    if rows.numel() == 0:  # every batch is empty (an epoch that picked nothing): every model stays as it is
+        return status
+    ws_bytes = int(_lib.load().ce_sgd_partial_fit_workspace_bytes(rows.numel(), C))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device) if ws_bytes else None  # written before it is read
+    call("ce_sgd_partial_fit", _p(X), F, D, X.stride(0), _p(rows), _p(labels), _p(row_offsets), U, C, float(alpha),
+         optimal_init, _p(seeds), SGD_GRADS[grad], _p(coef), _p(intercept), _p(t), _p(status), _p(ws), ws_bytes,
+         _stream(X.device))
+    return status
+
+
 def batch_rows(songs, frame_offsets, frame_perm=None, song_labels=None, item_offsets=None, n_classes=None):
     """From picked songs to X_batch's rows -- amg_test.py:491,
     ``X_train[X_train.index.isin(q_songs)]``, for one user or U: the frame rows

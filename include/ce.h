@@ -248,6 +248,67 @@ int ce_gnb_partial_fit(const double *X, int64_t F, int32_t D, int64_t ld, const 
                        double *class_prior, double *epsilon, ce_stream_t stream);
 
 /*
+ * SGDClassifier.partial_fit on the device -- replaces
+ * amg_test.py:509, mod.partial_fit(X_batch.values, y_batch_enc), for the
+ * reference's 'classifier_sgd' member (deam_classifier.py:214-217: loss='log',
+ * penalty='l2', learning_rate='optimal', fit_intercept, shuffle, no averaging,
+ * no class or sample weights), U models in one launch, one workgroup per model,
+ * one wave per binary problem.  Model u's batch is the rows
+ * rows[row_offsets[u] .. row_offsets[u+1]) of X [F, D] f64 (row stride ld),
+ * row i of class labels[i]; coef [U, K, D], intercept [U, K] and t [U] (f64:
+ * coef_, intercept_, t_) are updated IN PLACE.  K = C one-vs-rest problems for
+ * C > 2 (problem k: class k positive), K = 1 for C = 2 (class 1 positive), as
+ * in ce_sgd_predict_proba.  One epoch of sklearn's _plain_sgd64 per problem,
+ * operation for operation (read from sklearn 1.7.2):
+ *   1. the visiting order: the identity over the model's n rows, then for i in
+ *      0 .. n-2: j = i + our_rand_r(&seed) % (n - i), swap ind[i], ind[j];
+ *      our_rand_r is the xorshift (13, 17, 5) on a uint32 (0 becomes 1), taken
+ *      modulo 2^31.  seed = shuffle_seeds[u * K + k] (DEVICE memory), which the
+ *      host derives from random_state (ce_amd.ops.sgd_chain_seeds): the K
+ *      problems visit the same batch in K different orders;
+ *   2. per visited row x of class y (1.0 if positive, else 0.0), with wscale = 1
+ *      at the start and t = the model's t at entry:
+ *        p = (sum_j w[j] * x[j]) * wscale + b, the products added one after the
+ *            other in feature order onto +0.0 (no FMA, no pairwise sum);
+ *        eta = 1 / (alpha * (optimal_init + t - 1)); optimal_init is the host
+ *            constant of learning_rate='optimal' (ce_amd.ops.sgd_optimal_init);
+ *        g = the gradient: grad 0 (sklearn >= 1.x, cgradient_half_binomial):
+ *            p > -37 ? ((1 - y) - y * exp(-p)) / (1 + exp(-p)) : exp(p) - y;
+ *            grad 1 (sklearn 0.24.1, Log.dloss on labels ys = +-1, z = p * ys):
+ *            z > 18 ? exp(-z) * -ys : z < -18 ? -ys : -ys / (exp(z) + 1);
+ *            exp is glibc's; g is clipped to +-1e12; update = -eta * g;
+ *        wscale *= max(0, 1 - eta * alpha); if wscale < 1e-9: w *= wscale,
+ *            wscale = 1 (before the add);
+ *        if update != 0: w += x * (update / wscale), b += update;
+ *        t += 1;
+ *   3. w *= wscale after the last row; the model's t += n, once per model.
+ * Bit-identical to sklearn 1.7.2 with grad 0 for 1 <= D <= 512, 2 <= C <= 8;
+ * parity of grad 1 with the reference's pinned 0.24.1 is unpinned.  A model
+ * with an empty batch is left untouched, its t included.
+ * status [U] int32 is only ever SET: to 1 where a model's intercept or any
+ * weight is non-finite after the update (where sklearn raises ValueError; the
+ * parameters are left as the arithmetic produced them), to 2 where a model
+ * was not run (a batch of 2^31 rows or more, or one whose permutations need a
+ * workspace the call did not get); zero it before the call.
+ * The K permutations of a model stay in shared memory while K * n <= 8192;
+ * a larger batch keeps them in `workspace` (4-byte aligned, may be NULL when no
+ * batch is that large), ce_sgd_partial_fit_workspace_bytes(R, C) bytes for R
+ * rows in all (0: no batch can need it).  Preconditions as ce_gnb_partial_fit:
+ * every row in [0, F), every label in [0, C), row order = X_train's (the
+ * shuffle starts from the order given).  rows, labels, row_offsets [U + 1],
+ * shuffle_seeds: DEVICE memory.  Bad shapes, alpha or optimal_init not positive
+ * and finite, an unknown grad or a null pointer: CE_EINVAL; D > 512 or C > 8:
+ * CE_EUNSUPPORTED -- before any launch.  No allocation; stream-ordered and
+ * capturable.
+ */
+size_t ce_sgd_partial_fit_workspace_bytes(int64_t R, int32_t C);
+int ce_sgd_partial_fit(const double *X, int64_t F, int32_t D, int64_t ld, const int64_t *rows,
+                       const int32_t *labels, const int64_t *row_offsets, int32_t U, int32_t C,
+                       double alpha, double optimal_init, const uint32_t *shuffle_seeds, int32_t grad,
+                       double *coef, double *intercept, double *t, int32_t *status, void *workspace,
+                       size_t workspace_bytes, ce_stream_t stream);
+
+/*
  * XGBClassifier.predict_proba on the device (the
  * 'classifier_xgb' member; amg_test.py:435/:467 -> xgboost/sklearn.py:991-1029
  * -> libxgboost 1.3.3 CPU predictor, restated in csrc/ce_xgb.hip).
