@@ -114,6 +114,9 @@ class BatchedSelectionSession:
                 if f_perm.shape[0] < f_off[-1] or (f_perm < 0).any():
                     raise ValueError(f"frame_perm must hold frame_offsets[-1] = {int(f_off[-1])} row indices >= 0")
             self._F = int(f_off[-1])
+            self._song_frames = int(np.diff(f_off).max()) if len(f_off) > 1 else 0  # the longest song
+            # rows of X the geometry names (host numbers: a member's predict_proba_session checks X against it)
+            self._rows = int(f_perm[:self._F].max()) + 1 if f_perm is not None and self._F else self._F
         self.remaining = self.n_items.copy()
         # ---- device state
         self.dev = _device(device)

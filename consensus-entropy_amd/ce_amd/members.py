@@ -47,7 +47,34 @@ def _picks_batch(session, picks, song_labels, U, C, dev):
         songs = pad
     if not isinstance(songs, torch.Tensor):
         songs = torch.from_numpy(np.ascontiguousarray(songs, dtype=np.int64)).to(dev)
-    return ops.batch_rows(songs, f_off, f_perm, song_labels=song_labels, item_offsets=items, n_classes=C)
+    max_rows = None
+    if isinstance(songs, torch.Tensor) and songs.is_cuda and torch.cuda.is_current_stream_capturing():
+        # a capture cannot read the batch's size back: the rows are padded to a host bound instead --
+        # every picked slot a song of the longest kind, and never more than the pool's frames
+        max_rows = min(session._F, songs.numel() * session._song_frames)
+    return ops.batch_rows(songs, f_off, f_perm, song_labels=song_labels, item_offsets=items, n_classes=C,
+                          max_rows=max_rows)
+
+
+def _session_predict(session, X, U, D, C, out, skip_excluded):
+    """What a member's predict_proba_session hands to the users form of its
+    predict_proba: the session's frame geometry and bitmap, checked against the
+    member (U models, D features, C classes) and X from host numbers alone --
+    nothing is read back.  Returns the keyword arguments of ops.*_predict_proba_users."""
+    f_off, f_perm, items = session.frame_geometry()
+    users = 1 if items is None else items.numel() - 1
+    if users != U:
+        raise ValueError(f"the session has {users} user(s), this member {U} model(s)")
+    if items is None:
+        items = session._items  # a SelectionSession: one model owning every song
+    if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.shape[1] != D:
+        raise ValueError(f"X must be a float64 [F, D={D}] tensor")
+    if X.shape[0] < session._rows:
+        raise ValueError(f"X has {X.shape[0]} rows, the session's frame geometry names {session._rows}")
+    if out is not None:
+        ops.check_users_out(out, X.shape[0], C)
+    return dict(item_offsets=items, frame_offsets=f_off, frame_perm=f_perm,
+                excl=session.excl if skip_excluded else None, out=out)
 
 
 class DeviceGaussianNB:
@@ -81,6 +108,22 @@ class DeviceGaussianNB:
     def predict_proba(self, X, u=0, out=None):
         """Model u's predict_proba over the frames X [F, D] (ops.gnb_predict_proba, the device prior)."""
         return ops.gnb_predict_proba(X, self.theta[u], self.var[u], self.class_prior[u], out=out)
+
+    def predict_proba_session(self, X, session, out=None, skip_excluded=True):
+        """The predict step of an epoch (amg_test.py:435) for every model in
+        one launch (ops.gnb_predict_proba_users): every frame row of X [F, D]
+        owned by a song of the session is predicted by the model of the user
+        who owns it -- bit for bit ``predict_proba(X, u)`` on that row.
+        ``session``: a SelectionSession built with ``s_id`` (one model owning
+        every song) or a BatchedSelectionSession built with ``frame_offsets``
+        (one model per user).  skip_excluded: the rows of the songs already
+        picked are not written (and mostly not read) -- the session's
+        ``frames=`` epochs read no row of an excluded song; False writes every
+        owned row.  ``out``: an optional float64 [F, C] view (unit column
+        stride); rows it does not write keep what they held, and a new tensor
+        is zero there.  Nothing is synchronised or read back."""
+        kw = _session_predict(session, X, self.U, self.D, self.C, out, skip_excluded)
+        return ops.gnb_predict_proba_users(X, self.theta, self.var, self.class_prior, **kw)
 
     def partial_fit(self, X, rows, labels, row_offsets=None):
         """mod.partial_fit(X[rows], labels) for every model, in place: model u
@@ -160,6 +203,13 @@ class DeviceSGDClassifier:
     def predict_proba(self, X, u=0, out=None):
         """Model u's predict_proba over the frames X [F, D] (ops.sgd_predict_proba)."""
         return ops.sgd_predict_proba(X, self.coef[u], self.intercept[u], out=out)
+
+    def predict_proba_session(self, X, session, out=None, skip_excluded=True):
+        """The predict step of an epoch for every model in one launch
+        (ops.sgd_predict_proba_users), as DeviceGaussianNB.predict_proba_session:
+        bit for bit ``predict_proba(X, u)`` on every row user u owns."""
+        kw = _session_predict(session, X, self.U, self.D, self.C, out, skip_excluded)
+        return ops.sgd_predict_proba_users(X, self.coef, self.intercept, **kw)
 
     def partial_fit(self, X, rows, labels, row_offsets=None):
         """mod.partial_fit(X[rows], labels) for every model, in place: model u

@@ -550,6 +550,93 @@ def sgd_predict_proba(X, coef, intercept, out=None):
     return out
 
 
+def check_users_out(out, F, C):
+    """``out`` of the users forms: a float64 [F, C] view with unit column stride and rows that do not overlap."""
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.dim() != 2 or \
+            tuple(out.shape) != (F, C) or (C > 1 and out.stride(1) != 1) or (F > 1 and out.stride(0) < C):
+        raise ValueError(f"out must be a float64 [F={F}, C={C}] view with unit column stride")
+
+
+def _users_args(X, C, item_offsets, frame_offsets, frame_perm, excl, out):
+    """The tail the users forms share: the sessions' geometry (frame_geometry)
+    as the C-ABI reads it, the songs' bitmap and ``out``.  Returns
+    (U, item_offsets, frame_offsets, frame_perm, out)."""
+    F = X.shape[0]
+    item_offsets = _i64(item_offsets, "item_offsets").reshape(-1)
+    frame_offsets = _i64(frame_offsets, "frame_offsets").reshape(-1)
+    U = item_offsets.numel() - 1
+    if U < 1 or frame_offsets.numel() < 1:
+        raise ValueError("item_offsets must hold U + 1 >= 2 entries and frame_offsets total_items + 1 >= 1")
+    if frame_perm is not None:
+        frame_perm = _i64(frame_perm, "frame_perm").reshape(-1)
+    if excl is not None:
+        _check_excl(excl, frame_offsets.numel() - 1)
+    if out is None:
+        # rows of excluded songs are not written: a new tensor is zero there, the rule of frames_consensus
+        out = (torch.zeros if excl is not None else torch.empty)((F, C), dtype=torch.float64, device=X.device)
+    _on_gpu(out, "out")
+    check_users_out(out, F, C)
+    return U, item_offsets, frame_offsets, frame_perm, out
+
+
+def gnb_predict_proba_users(X, theta, var, class_prior, item_offsets, frame_offsets, frame_perm=None, excl=None,
+                            out=None):
+    """gnb_predict_proba for U models at once (ce_gnb_predict_proba_users): every
+    frame row of X [F, D] is predicted by the model of the user who owns it, in
+    one launch.  theta / var [U, C, D], class_prior [U, C] (device tensors: the
+    log-prior is one ``log_f64`` over the flat priors, as the one-model path
+    computes it for a device prior; a zero prior gives -inf).  The geometry is
+    a session's ``frame_geometry()``: stacked song g owns the rows
+    frame_perm[frame_offsets[g]:frame_offsets[g+1]] (or that range itself),
+    user u the stacked songs item_offsets[u]:item_offsets[u+1].  excl: an
+    optional exclusion bitmap over the stacked songs; rows of excluded songs
+    are NOT written and, eight consecutive frames at a time, not read.  Rows no
+    song owns are not written either, and a frame_perm entry outside [0, F) is
+    skipped.  out: an optional float64 [F, C] view with unit column stride (a
+    new tensor is zero-filled when ``excl`` is given).  Per row the bits are
+    gnb_predict_proba's.  Nothing is synchronised."""
+    F, D = _check_X(X)
+    theta = _f64_dev(theta, X.device, "theta")
+    var = _f64_dev(var, X.device, "var")
+    if theta.dim() != 3 or theta.shape[2] != D or tuple(var.shape) != tuple(theta.shape):
+        raise ValueError(f"theta/var must be [U, C, {D}]")
+    Um, C = theta.shape[:2]
+    _on_gpu(class_prior, "class_prior")
+    if class_prior.numel() != Um * C:
+        raise ValueError(f"class_prior must be [U={Um}, C={C}]")
+    U, item_offsets, frame_offsets, frame_perm, out = _users_args(X, C, item_offsets, frame_offsets, frame_perm, excl, out)
+    if U != Um:
+        raise ValueError(f"item_offsets names {U} user(s), theta holds {Um} model(s)")
+    log_prior = log_f64(class_prior.to(device=X.device, dtype=torch.float64).reshape(-1).contiguous())
+    call("ce_gnb_predict_proba_users", _p(X), F, D, X.stride(0), _p(theta), _p(var), _p(log_prior), C, U,
+         _p(item_offsets), _p(frame_offsets), _p(frame_perm), _p(excl), _p(out), max(out.stride(0), C),
+         _stream(X.device))
+    return out
+
+
+def sgd_predict_proba_users(X, coef, intercept, item_offsets, frame_offsets, frame_perm=None, excl=None, out=None):
+    """sgd_predict_proba for U models at once (ce_sgd_predict_proba_users): coef
+    [U, K, D], intercept [U, K]; K = C (OvR) or 1 (binary, C = 2).  Geometry,
+    ``excl`` and ``out`` as gnb_predict_proba_users; per row the bits are
+    sgd_predict_proba's."""
+    F, D = _check_X(X)
+    coef = _f64_dev(coef, X.device, "coef")
+    if coef.dim() != 3 or coef.shape[2] != D:
+        raise ValueError(f"coef must be [U, K, {D}]")
+    Um, K = coef.shape[:2]
+    intercept = _f64_dev(intercept, X.device, "intercept").reshape(-1)
+    if intercept.numel() != Um * K:
+        raise ValueError(f"intercept must be [U={Um}, K={K}]")
+    C = 2 if K == 1 else K
+    U, item_offsets, frame_offsets, frame_perm, out = _users_args(X, C, item_offsets, frame_offsets, frame_perm, excl, out)
+    if U != Um:
+        raise ValueError(f"item_offsets names {U} user(s), coef holds {Um} model(s)")
+    call("ce_sgd_predict_proba_users", _p(X), F, D, X.stride(0), _p(coef), _p(intercept), K, C, U,
+         _p(item_offsets), _p(frame_offsets), _p(frame_perm), _p(excl), _p(out), max(out.stride(0), C),
+         _stream(X.device))
+    return out
+
+
 def _fit_state(t, what, shape=None):
     """A tensor the partial_fit updates in place: float64, contiguous, on the device (no copy may stand in)."""
     _on_gpu(t, what)
@@ -725,7 +812,8 @@ def sgd_partial_fit(X, rows, labels, coef, intercept, t, row_offsets=None, alpha
     return status
 
 
-def batch_rows(songs, frame_offsets, frame_perm=None, song_labels=None, item_offsets=None, n_classes=None):
+def batch_rows(songs, frame_offsets, frame_perm=None, song_labels=None, item_offsets=None, n_classes=None,
+               max_rows=None):
     """From picked songs to X_batch's rows -- amg_test.py:491,
     ``X_train[X_train.index.isin(q_songs)]``, for one user or U: the frame rows
     of the picked songs in X_train's order (ascending row, not pick order), a
@@ -741,7 +829,12 @@ def batch_rows(songs, frame_offsets, frame_perm=None, song_labels=None, item_off
     Returns (rows int64 [R], labels int32 [R], row_offsets int64 [U + 1]), each
     user's rows ascending, on frame_offsets' device -- torch ops only, so CPU
     tensors work too; R is the one size read back from the device
-    (repeat_interleave), everything else is sorts, scans and scatters."""
+    (repeat_interleave), everything else is sorts, scans and scatters.
+    ``max_rows`` (a host number no batch exceeds, e.g. the pool's frame count):
+    nothing is read back -- what a HIP-graph capture needs; rows and labels
+    then hold max_rows entries, the R = row_offsets[U] real ones first and
+    padding (an in-range row, owned by no model) behind them, which the
+    partial_fit kernels never read."""
     if not isinstance(frame_offsets, torch.Tensor):
         frame_offsets = torch.as_tensor(np.asarray(frame_offsets, dtype=np.int64))
     dev = frame_offsets.device
@@ -779,7 +872,7 @@ def batch_rows(songs, frame_offsets, frame_perm=None, song_labels=None, item_off
         G, pool = S + io[:-1].unsqueeze(1), (io[1:] - io[:-1]).unsqueeze(1)
     else:
         G, pool = S, n_songs
-    if n_songs == 0 or S.numel() == 0:
+    if n_songs == 0 or S.numel() == 0 or (max_rows is not None and int(max_rows) <= 0):
         return S.new_zeros(0), torch.zeros(0, dtype=torch.int32, device=dev), row_offsets
     # (user, song) keys in user-then-song order; a slot that names no song gets the key past every user
     user = torch.arange(U, device=dev).unsqueeze(1)
@@ -789,10 +882,18 @@ def batch_rows(songs, frame_offsets, frame_perm=None, song_labels=None, item_off
     first[1:] &= key[1:] != key[:-1]
     uu, g = (key // n_songs).clamp(max=U - 1), key % n_songs
     cnt = torch.where(first, off[g + 1] - off[g], 0)
-    seg = torch.repeat_interleave(torch.arange(key.numel(), device=dev), cnt)  # the one size read-back
+    slots = torch.arange(key.numel(), device=dev)
+    if max_rows is None:
+        seg = torch.repeat_interleave(slots, cnt)  # the one size read-back
+    else:  # a fixed size: output entry i belongs to the first slot whose running count passes i
+        out_i, total = torch.arange(int(max_rows), device=dev), torch.cumsum(cnt, 0)
+        real = out_i < total[-1]
+        seg = torch.where(real, torch.searchsorted(total, out_i, right=True).clamp(max=key.numel() - 1), 0)
     start = torch.cumsum(cnt, 0) - cnt
     rows = off[g][seg] + (torch.arange(seg.numel(), device=dev) - start[seg])
     ruser, rlab = uu[seg], lab[g][seg]
+    if max_rows is not None:  # padding: position 0, past every user
+        rows, ruser = torch.where(real, rows, 0), torch.where(real, ruser, U)
     if frame_perm is not None:  # permuted frames: a song's rows are scattered, so order each user's rows again
         rows = idx(frame_perm).reshape(-1)[rows]
         rows, o = torch.sort(rows, stable=True)

@@ -122,6 +122,9 @@ class SelectionSession:
             self.song_ids, n, self._F, self._f_off, self._f_perm = groupby_device(s_id, self.dev)
             if n != self.N:
                 raise ValueError(f"s_id names {n} songs, n_items is {self.N}")
+            self._rows = self._F  # rows of X the geometry names: the grouping permutation covers 0 .. F - 1
+            self._song_frames = int(np.unique(np.asarray(getattr(s_id, "values", s_id)), return_counts=True)[1].max()) if n else 0
+            self._items = torch.tensor([0, n], dtype=torch.int64).to(self.dev)  # one user owning every song
         self.rng = rng
         self.H = None
         if mode in ("hc", "mix"):

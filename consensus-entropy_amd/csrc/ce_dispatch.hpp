@@ -92,6 +92,17 @@ static inline int with_wide_v(const CommArgs& a, F&& f) {
     return CE_EUNSUPPORTED;
 }
 
+// ---- member inference dispatch (ce_members.hpp, ce_members_users.hpp) --------
+// features per lane of the 8-lanes-per-frame kernels: ceil(D / 8), rounded up to a multiple of 8
+template <class F>
+static inline int with_nx(int D, F&& f) {
+    const int nx = (D + 7) / 8;
+#define CE_NX(N_) if (nx <= N_) { f(std::integral_constant<int, N_>()); return CE_OK; }
+    CE_NX(8) CE_NX(16) CE_NX(24) CE_NX(32) CE_NX(36) CE_NX(40) CE_NX(48) CE_NX(56) CE_NX(64)
+#undef CE_NX
+    return CE_EUNSUPPORTED;
+}
+
 // Blocks of `kernel` resident on the whole device (occupancy API x CUs), cached.
 static inline int device_cus() {
     static int cus[64] = {0};

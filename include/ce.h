@@ -210,6 +210,36 @@ int ce_sgd_predict_proba(const double *X, int64_t F, int32_t D, int64_t ld, cons
                          ce_stream_t stream);
 
 /*
+ * The users form of the two entry points above: after the
+ * partial_fit entry points below every user has a model of their own, and one
+ * launch predicts every frame row with the model of the user who owns it.
+ * theta / var [U, C, D], log_prior [U, C] (coef [U, K, D], intercept [U, K]):
+ * model u's parameters at u * C * D (u * K * D).  The geometry is the
+ * sessions': stacked song g owns the CSR positions frame_offsets[g] ..
+ * frame_offsets[g+1], position p being row frame_perm[p] of X (row p when
+ * frame_perm is NULL); user u owns the stacked songs item_offsets[u] ..
+ * item_offsets[u+1] (DEVICE arrays, [T + 1], [>= frame_offsets[T]], [U + 1];
+ * non-decreasing offsets, item_offsets[U] <= T).  A row of X that no song owns
+ * is not touched in out; a position whose row is outside [0, F) is skipped
+ * (neither read nor written).  excl_or_null: an exclusion bitmap over the T
+ * stacked songs (ce_excl_words(T) words): the rows of an excluded song are
+ * never written, and their frames are not read where eight consecutive
+ * positions are excluded.  Per row the arithmetic is that of the one-model
+ * entry points, bit for bit.  Shapes as there (GaussianNB: D >= 8); U >= 1;
+ * F == 0 launches nothing.  One launch, no workspace, nothing synchronised.
+ */
+int ce_gnb_predict_proba_users(const double *X, int64_t F, int32_t D, int64_t ld, const double *theta,
+                               const double *var, const double *log_prior, int32_t C, int32_t U,
+                               const int64_t *item_offsets, const int64_t *frame_offsets,
+                               const int64_t *frame_perm_or_null, const uint32_t *excl_or_null,
+                               double *out, int64_t ld_out, ce_stream_t stream);
+int ce_sgd_predict_proba_users(const double *X, int64_t F, int32_t D, int64_t ld, const double *coef,
+                               const double *intercept, int32_t K, int32_t C, int32_t U,
+                               const int64_t *item_offsets, const int64_t *frame_offsets,
+                               const int64_t *frame_perm_or_null, const uint32_t *excl_or_null,
+                               double *out, int64_t ld_out, ce_stream_t stream);
+
+/*
  * GaussianNB.partial_fit on the device -- replaces
  * amg_test.py:509, mod.partial_fit(X_batch.values, y_batch_enc), the retrain
  * step of an epoch, for U already-fitted models (priors=None) in one launch,
