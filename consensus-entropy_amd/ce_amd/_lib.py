@@ -41,6 +41,11 @@ SIGNATURES = {
                                           _vp]),
     "ce_sgd_predict_proba_users": (_int, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                           _i64, _vp]),
+    "ce_gnb_score_users": (_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _i64, _vp]),
+    "ce_sgd_score_users": (_int, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _i64, _vp]),
+    "ce_f1_weighted_users": (_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "ce_gnb_partial_fit": (_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _i32, ctypes.c_double, _vp, _vp, _vp, _vp,
                                   _vp, _vp]),
     "ce_sgd_partial_fit_workspace_bytes": (_sz, [_i64, _i32]),

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .select import _device
+from .select import _device, groupby_device
 
 
 def _own_f64(a, dev):
@@ -77,6 +77,112 @@ def _session_predict(session, X, U, D, C, out, skip_excluded):
                 excl=session.excl if skip_excluded else None, out=out)
 
 
+def _host_offsets(a, what):
+    """Offsets as host numbers (an int64 array): what the shapes are checked from."""
+    o = np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.int64).reshape(-1)
+    if o.shape[0] < 1 or o[0] < 0 or (np.diff(o) < 0).any():
+        raise ValueError(f"{what} must hold non-decreasing entries >= 0")
+    return o
+
+
+class EvalSet:
+    """Every user's test set on the device (amg_test.py:356-366: X_test /
+    y_test, the frame rows of the user's test songs), in the sessions' geometry:
+    stacked test song g owns the rows ``frame_perm[frame_offsets[g]:
+    frame_offsets[g+1]]`` of X (or that range itself), user u the stacked songs
+    ``item_offsets[u]:item_offsets[u+1]`` (None: one user owning every song).
+    X [F, D] float64, y [F] the encoded class of every ROW of X, 0 .. C-1 (a row
+    with any other label is not counted).  ``excl``: an optional exclusion
+    bitmap over the stacked songs (ops.excl_bitmap), None by default."""
+
+    def __init__(self, X, y, frame_offsets, item_offsets=None, frame_perm=None, device=None):
+        f_off = _host_offsets(frame_offsets, "frame_offsets")
+        T = f_off.shape[0] - 1
+        items = np.array([0, T], np.int64) if item_offsets is None else _host_offsets(item_offsets, "item_offsets")
+        if items.shape[0] < 2:
+            raise ValueError("item_offsets must hold U + 1 >= 2 entries")
+        if items[-1] > T:
+            raise ValueError(f"item_offsets names {int(items[-1])} songs, frame_offsets holds T + 1 = {T + 1} entries")
+        self.U, self.T, n = items.shape[0] - 1, T, int(f_off[-1])
+        f_perm = None
+        if frame_perm is not None:
+            f_perm = np.asarray(frame_perm.cpu() if isinstance(frame_perm, torch.Tensor) else frame_perm,
+                                dtype=np.int64).reshape(-1)
+            if f_perm.shape[0] < n or (f_perm < 0).any():
+                raise ValueError(f"frame_perm must hold frame_offsets[-1] = {n} row indices >= 0")
+        self._rows = int(f_perm[:n].max()) + 1 if f_perm is not None and n else n  # rows of X the geometry names
+        if not isinstance(X, torch.Tensor):
+            X = torch.from_numpy(np.ascontiguousarray(getattr(X, "values", X), dtype=np.float64))
+        if X.dim() != 2 or X.dtype != torch.float64:
+            raise ValueError("X must be a float64 [F, D] tensor")
+        if X.shape[0] < self._rows:
+            raise ValueError(f"X has {X.shape[0]} rows, the frame geometry names {self._rows}")
+        if not isinstance(y, torch.Tensor):
+            y = torch.from_numpy(np.ascontiguousarray(getattr(y, "values", y)))
+        if y.dim() != 1 or y.shape[0] != X.shape[0] or y.dtype.is_floating_point or y.dtype == torch.bool:
+            raise ValueError(f"y must hold one integer class per row of X ({X.shape[0]})")
+        self.dev = _device(device if device is not None or not X.is_cuda else X.device)
+        self.X = X.to(self.dev)
+        if self.X.stride(1) != 1:
+            self.X = self.X.contiguous()
+        self.y = y.to(device=self.dev, dtype=torch.int32).contiguous()
+        self.F, self.D = self.X.shape
+        self.frame_offsets = torch.from_numpy(f_off).to(self.dev)
+        self.item_offsets = torch.from_numpy(items).to(self.dev)
+        self.frame_perm = torch.from_numpy(f_perm).to(self.dev) if f_perm is not None else None
+        self.excl = None
+
+    @classmethod
+    def from_s_id(cls, X, y, s_id, item_offsets=None, device=None):
+        """The test set of pandas frames: ``s_id`` names the song of every row
+        of X.  The songs are the sorted unique ids and a song's rows keep their
+        order -- groupby(['s_id']), the same rule as the sessions (groupby_device);
+        item_offsets counts those sorted songs per user."""
+        dev = _device(device if device is not None or not (isinstance(X, torch.Tensor) and X.is_cuda) else X.device)
+        _, _, _, f_off, f_perm = groupby_device(s_id, dev)
+        return cls(X, y, f_off, item_offsets, f_perm, device=dev)
+
+    def frame_geometry(self):
+        """(frame_offsets [T + 1], frame_perm or None, item_offsets [U + 1]) on the device, as a session's."""
+        return self.frame_offsets, self.frame_perm, self.item_offsets
+
+
+def _evalset_args(evalset, U, D):
+    """What a member's ``evaluate`` hands to ops.*_score_users: the set's
+    geometry, checked against the member from host numbers alone."""
+    if not isinstance(evalset, EvalSet):
+        raise TypeError("evaluate needs a ce_amd.EvalSet")
+    f_off, f_perm, items = evalset.frame_geometry()
+    if evalset.U != U:
+        raise ValueError(f"the EvalSet has {evalset.U} user(s), this member {U} model(s)")
+    if evalset.D != D:
+        raise ValueError(f"the EvalSet has {evalset.D} features, this member {D}")
+    return dict(item_offsets=items, frame_offsets=f_off, frame_perm=f_perm, excl=evalset.excl, y=evalset.y)
+
+
+def mean_f1(f1_list):
+    """np.mean(f1_list) of amg_test.py:518 for every user, on the device: the
+    members' f1 [U] tensors added one after the other in list order onto 0.0
+    and divided by their count -- numpy's bits for fewer than 8 members (its
+    pairwise sum adds in order below 8 terms)."""
+    f1_list = list(f1_list)
+    if not f1_list:
+        raise ValueError("mean_f1 needs at least one member's f1")
+    if len(f1_list) >= 8:
+        raise ValueError("mean_f1 restates np.mean for fewer than 8 members")
+    s = torch.zeros_like(f1_list[0])
+    for f in f1_list:
+        s = s + f
+    return s / float(len(f1_list))
+
+
+def _f1_of(cm, report):
+    if report:
+        f1, prf = ops.f1_weighted_users(cm, report=True)
+        return f1, cm, prf
+    return ops.f1_weighted_users(cm), cm
+
+
 class DeviceGaussianNB:
     """U fitted GaussianNB models (priors=None) on the device.  theta / var
     [U, C, D] (theta_, var_ -- sigma_ in sklearn 0.24), class_count [U, C]
@@ -124,6 +230,19 @@ class DeviceGaussianNB:
         is zero there.  Nothing is synchronised or read back."""
         kw = _session_predict(session, X, self.U, self.D, self.C, out, skip_excluded)
         return ops.gnb_predict_proba_users(X, self.theta, self.var, self.class_prior, **kw)
+
+    def evaluate(self, evalset, report=False):
+        """The evaluate step of an epoch (amg_test.py:513-515, and :411-413
+        before epoch 0) for every model: one score launch (ops.gnb_score_users:
+        ``mod.predict`` of every user's test frames, counted against their
+        labels) and one F1 launch (ops.f1_weighted_users: sklearn's
+        ``f1_score(average='weighted')``).  ``evalset``: a ce_amd.EvalSet.
+        Returns (f1 [U], cm [U, C, C]), or (f1, cm, prf [U, C, 4]) with
+        report=True -- the per-class precision, recall, F1 and support of
+        classification_report (:514).  Nothing is synchronised or read back."""
+        kw = _evalset_args(evalset, self.U, self.D)
+        cm, _, _ = ops.gnb_score_users(evalset.X, self.theta, self.var, self.class_prior, **kw)
+        return _f1_of(cm, report)
 
     def partial_fit(self, X, rows, labels, row_offsets=None):
         """mod.partial_fit(X[rows], labels) for every model, in place: model u
@@ -210,6 +329,14 @@ class DeviceSGDClassifier:
         bit for bit ``predict_proba(X, u)`` on every row user u owns."""
         kw = _session_predict(session, X, self.U, self.D, self.C, out, skip_excluded)
         return ops.sgd_predict_proba_users(X, self.coef, self.intercept, **kw)
+
+    def evaluate(self, evalset, report=False):
+        """The evaluate step of an epoch for every model, as
+        DeviceGaussianNB.evaluate (ops.sgd_score_users, ops.f1_weighted_users):
+        returns (f1 [U], cm [U, C, C]), and prf [U, C, 4] with report=True."""
+        kw = _evalset_args(evalset, self.U, self.D)
+        cm, _, _ = ops.sgd_score_users(evalset.X, self.coef, self.intercept, **kw)
+        return _f1_of(cm, report)
 
     def partial_fit(self, X, rows, labels, row_offsets=None):
         """mod.partial_fit(X[rows], labels) for every model, in place: model u

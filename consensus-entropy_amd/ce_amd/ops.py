@@ -637,6 +637,114 @@ def sgd_predict_proba_users(X, coef, intercept, item_offsets, frame_offsets, fra
     return out
 
 
+def _labels_i32(y, F):
+    """The labels of a score launch as the C-ABI reads them: one encoded class per ROW of X, int32 [F] on the device."""
+    _on_gpu(y, "y")
+    if y.dim() != 1 or y.numel() != F or y.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+        raise ValueError(f"y must be an integer [F={F}] tensor: one encoded class per row of X")
+    if y.dtype == torch.int32 and y.is_contiguous():
+        return y
+    return y.to(torch.int32).contiguous()
+
+
+def _score_args(X, C, score_cols, U_models, item_offsets, frame_offsets, frame_perm, excl, y, return_pred,
+                return_scores):
+    """The tail the two score launches share.  Returns (U, item_offsets,
+    frame_offsets, frame_perm, y, cm, pred, scores): cm a new int64 [U, C, C]
+    (the entry point zero-fills it), pred a new int32 [F] of -1 and scores a new
+    float64 [F, score_cols] of NaN where asked for -- what a row that is not
+    counted keeps."""
+    F = X.shape[0]
+    item_offsets = _i64(item_offsets, "item_offsets").reshape(-1)
+    frame_offsets = _i64(frame_offsets, "frame_offsets").reshape(-1)
+    U = item_offsets.numel() - 1
+    if U < 1 or frame_offsets.numel() < 1:
+        raise ValueError("item_offsets must hold U + 1 >= 2 entries and frame_offsets total_items + 1 >= 1")
+    if U != U_models:
+        raise ValueError(f"item_offsets names {U} user(s), the member holds {U_models} model(s)")
+    if frame_perm is not None:
+        frame_perm = _i64(frame_perm, "frame_perm").reshape(-1)
+    if excl is not None:
+        _check_excl(excl, frame_offsets.numel() - 1)
+    y = _labels_i32(y, F)
+    cm = torch.empty((U, C, C), dtype=torch.int64, device=X.device)
+    pred = torch.full((F,), -1, dtype=torch.int32, device=X.device) if return_pred else None
+    scores = torch.full((F, score_cols), math.nan, dtype=torch.float64, device=X.device) if return_scores else None
+    return U, item_offsets, frame_offsets, frame_perm, y, cm, pred, scores
+
+
+def gnb_score_users(X, theta, var, class_prior, item_offsets, frame_offsets, y, frame_perm=None, excl=None,
+                    return_pred=False, return_scores=False):
+    """The evaluate step of an epoch for U GaussianNB models in one launch
+    (ce_gnb_score_users; amg_test.py:513, ``mod.predict(X_test.values)``, and
+    the counts :515's f1_score is formed from).  X [F, D] f64 holds every
+    user's TEST frames, ``y`` [F] their encoded classes by row of X; the
+    geometry (an EvalSet's ``frame_geometry()``) and the models are those of
+    gnb_predict_proba_users.  Every owned row is labelled by the model of its
+    user -- np.argmax of the joint log-likelihood, whose bits are the ones
+    gnb_predict_proba_users forms before its logsumexp -- and counted in
+    cm[u, y, pred].  A row whose label is outside [0, C), whose song is
+    excluded or that no song owns is not counted.  Returns (cm int64 [U, C, C],
+    pred int32 [F] or None, scores f64 [F, C] or None); rows not counted keep
+    -1 in pred and NaN in scores.  Nothing is synchronised."""
+    F, D = _check_X(X)
+    theta = _f64_dev(theta, X.device, "theta")
+    var = _f64_dev(var, X.device, "var")
+    if theta.dim() != 3 or theta.shape[2] != D or tuple(var.shape) != tuple(theta.shape):
+        raise ValueError(f"theta/var must be [U, C, {D}]")
+    Um, C = theta.shape[:2]
+    _on_gpu(class_prior, "class_prior")
+    if class_prior.numel() != Um * C:
+        raise ValueError(f"class_prior must be [U={Um}, C={C}]")
+    U, item_offsets, frame_offsets, frame_perm, y, cm, pred, scores = _score_args(
+        X, C, C, Um, item_offsets, frame_offsets, frame_perm, excl, y, return_pred, return_scores)
+    log_prior = log_f64(class_prior.to(device=X.device, dtype=torch.float64).reshape(-1).contiguous())
+    call("ce_gnb_score_users", _p(X), F, D, X.stride(0), _p(theta), _p(var), _p(log_prior), C, U, _p(item_offsets),
+         _p(frame_offsets), _p(frame_perm), _p(excl), _p(y), _p(cm), _p(pred), _p(scores), C, _stream(X.device))
+    return cm, pred, scores
+
+
+def sgd_score_users(X, coef, intercept, item_offsets, frame_offsets, y, frame_perm=None, excl=None, return_pred=False,
+                    return_scores=False):
+    """gnb_score_users for U SGDClassifier models (ce_sgd_score_users): coef
+    [U, K, D], intercept [U, K]; K = C (one-vs-rest: np.argmax of the decision
+    values) or 1 (binary, C = 2: decision > 0 is class 1).  The decision values
+    are the ones sgd_predict_proba_users feeds to expit, bit for bit; scores is
+    [F, K]."""
+    F, D = _check_X(X)
+    coef = _f64_dev(coef, X.device, "coef")
+    if coef.dim() != 3 or coef.shape[2] != D:
+        raise ValueError(f"coef must be [U, K, {D}]")
+    Um, K = coef.shape[:2]
+    intercept = _f64_dev(intercept, X.device, "intercept").reshape(-1)
+    if intercept.numel() != Um * K:
+        raise ValueError(f"intercept must be [U={Um}, K={K}]")
+    C = 2 if K == 1 else K
+    U, item_offsets, frame_offsets, frame_perm, y, cm, pred, scores = _score_args(
+        X, C, K, Um, item_offsets, frame_offsets, frame_perm, excl, y, return_pred, return_scores)
+    call("ce_sgd_score_users", _p(X), F, D, X.stride(0), _p(coef), _p(intercept), K, C, U, _p(item_offsets),
+         _p(frame_offsets), _p(frame_perm), _p(excl), _p(y), _p(cm), _p(pred), _p(scores), K, _stream(X.device))
+    return cm, pred, scores
+
+
+def f1_weighted_users(cm, report=False):
+    """sklearn 1.7.2's ``f1_score(y_true, y_pred, average='weighted')`` of every
+    user from their counts (ce_f1_weighted_users; amg_test.py:515): cm int64
+    [U, C, C], cm[u, true, predicted].  Returns f1 f64 [U] (NaN for a user
+    without a counted row), and with report=True (f1, prf [U, C, 4]): every
+    class's precision, recall, F1 and support, the numbers of
+    classification_report (:514)."""
+    _on_gpu(cm, "cm")
+    if cm.dim() != 3 or cm.shape[1] != cm.shape[2] or cm.dtype != torch.int64 or cm.shape[0] < 1:
+        raise ValueError("cm must be an int64 [U, C, C] tensor")
+    cm = cm.contiguous()
+    U, C = cm.shape[:2]
+    f1 = torch.empty(U, dtype=torch.float64, device=cm.device)
+    prf = torch.empty((U, C, 4), dtype=torch.float64, device=cm.device) if report else None
+    call("ce_f1_weighted_users", _p(cm), U, C, _p(f1), _p(prf), _stream(cm.device))
+    return (f1, prf) if report else f1
+
+
 def _fit_state(t, what, shape=None):
     """A tensor the partial_fit updates in place: float64, contiguous, on the device (no copy may stand in)."""
     _on_gpu(t, what)

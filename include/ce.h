@@ -71,7 +71,7 @@ const char *ce_version(void);
  * rocprofv3 names it without "void " and the argument list (e.g.
  * "ce::k_stream_nmc<0, 4, 16, 2, false, 2>"); "" when that call launched none
  * of the noted kernels.  Lets a benchmark tie a profiled figure to the kernel
- * it actually ran. */
+ * it actually ran.  The ce_*_score_users entry points note their kernel too. */
 const char *ce_last_kernel(void);
 
 /*
@@ -337,6 +337,72 @@ int ce_sgd_partial_fit(const double *X, int64_t F, int32_t D, int64_t ld, const 
                        double alpha, double optimal_init, const uint32_t *shuffle_seeds, int32_t grad,
                        double *coef, double *intercept, double *t, int32_t *status, void *workspace,
                        size_t workspace_bytes, ce_stream_t stream);
+
+/*
+ * The evaluate step of an epoch for the linear members --
+ * replaces amg_test.py:513-515 (and :411-413 before epoch 0) for U models in
+ * one launch per member:
+ *   this_mod_pred = mod.predict(X_test.values)
+ *   f1_score(y_test_enc.values, this_mod_pred, average='weighted')
+ * ce_*_score_users label every TEST frame row with the model of the user who
+ * owns it and count (true class, predicted class) per user.  Models as in
+ * ce_*_predict_proba_users (theta / var [U, C, D], log_prior [U, C]; coef
+ * [U, K, D], intercept [U, K]); the geometry is theirs too, here over the test
+ * songs of every user: item_offsets [U + 1], frame_offsets [T + 1],
+ * frame_perm_or_null, excl_or_null, with the same skips (a position whose row
+ * is outside [0, F), the rows of an excluded song).  Per row the scores are the
+ * ones the predict_proba kernels form, bit for bit: GaussianNB the joint
+ * log-likelihood jll[c] (before the logsumexp), SGD the decision value
+ * x . coef_c + intercept_c (before expit).  The predicted class is sklearn's:
+ * np.argmax over the C scores (the FIRST maximum; a NaN wins at its first
+ * occurrence), and for a binary SGD model (K = 1) score > 0 ? 1 : 0 (NaN: 0) --
+ * not the argmax of the rounded probabilities.
+ *   y               [F] int32 by ROW of X: the encoded class 0 .. C-1.  A row
+ *                   whose label is outside [0, C) is not counted and nothing
+ *                   is written for it.
+ *   cm              [U, C, C] int64, cm[u, y, pred] = counted rows of user u.
+ *                   ZERO-FILLED by the entry point with one stream-ordered
+ *                   memset before the launch (under stream capture: one memset
+ *                   node), then added to with integer atomics: the same on
+ *                   every run.
+ *   pred_or_null    [F] int32 by row of X; rows that are not owned, excluded,
+ *                   out of range or whose label is are not written.
+ *   scores_or_null  [F, C] f64, row pitch ld_scores (>= C; >= 1 for a binary
+ *                   SGD model, which writes column 0 only); the same rows.
+ * Shapes and refusals as ce_*_predict_proba_users (GaussianNB: 8 <= D <= 512;
+ * SGD: 1 <= D <= 512), 2 <= C <= 8, U >= 1; y or cm NULL: CE_EINVAL.  F == 0
+ * zero-fills cm and launches nothing.  No workspace, nothing synchronised.
+ * ce_last_kernel() names the score kernel launched ("" when none was).
+ *
+ * ce_f1_weighted_users: cm [U, C, C] -> f1 [U] f64, sklearn 1.7.2's
+ * f1_score(average='weighted') restated (bit-identical; parity with the
+ * reference's pinned 0.24.1, which forms 2pr/(p+r), is unpinned):
+ *   true_c = sum_p cm[c, p], pred_c = sum_y cm[y, c], tp_c = cm[c, c];
+ *   class c is present iff true_c + pred_c > 0 (unique_labels(y_true, y_pred));
+ *   f_c = (2.0 * tp_c) / ((double)true_c + (double)pred_c);
+ *   s = the sum of f_c * true_c over the present classes in ascending c, added
+ *       one after the other onto 0.0 for fewer than 8 terms, by numpy's tree
+ *       ((t0+t1)+(t2+t3)) + ((t4+t5)+(t6+t7)) for 8;
+ *   f1 = s / sum_c true_c.
+ * A user without a counted row gets NaN (sklearn has no value there).
+ * prf_or_null [U, C, 4] f64: precision tp_c/pred_c, recall tp_c/true_c, f_c
+ * and the support true_c of every class (classification_report, :514), 0.0 on
+ * a zero denominator and for an absent class.  U >= 1, 2 <= C <= 8.
+ */
+int ce_gnb_score_users(const double *X, int64_t F, int32_t D, int64_t ld, const double *theta,
+                       const double *var, const double *log_prior, int32_t C, int32_t U,
+                       const int64_t *item_offsets, const int64_t *frame_offsets,
+                       const int64_t *frame_perm_or_null, const uint32_t *excl_or_null,
+                       const int32_t *y, int64_t *cm, int32_t *pred_or_null, double *scores_or_null,
+                       int64_t ld_scores, ce_stream_t stream);
+int ce_sgd_score_users(const double *X, int64_t F, int32_t D, int64_t ld, const double *coef,
+                       const double *intercept, int32_t K, int32_t C, int32_t U,
+                       const int64_t *item_offsets, const int64_t *frame_offsets,
+                       const int64_t *frame_perm_or_null, const uint32_t *excl_or_null,
+                       const int32_t *y, int64_t *cm, int32_t *pred_or_null, double *scores_or_null,
+                       int64_t ld_scores, ce_stream_t stream);
+int ce_f1_weighted_users(const int64_t *cm, int32_t U, int32_t C, double *f1, double *prf_or_null,
+                         ce_stream_t stream);
 
 /*
  * XGBClassifier.predict_proba on the device (the
