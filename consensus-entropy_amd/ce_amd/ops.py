@@ -557,11 +557,9 @@ def check_users_out(out, F, C):
         raise ValueError(f"out must be a float64 [F={F}, C={C}] view with unit column stride")
 
 
-def _users_args(X, C, item_offsets, frame_offsets, frame_perm, excl, out):
-    """The tail the users forms share: the sessions' geometry (frame_geometry)
-    as the C-ABI reads it, the songs' bitmap and ``out``.  Returns
-    (U, item_offsets, frame_offsets, frame_perm, out)."""
-    F = X.shape[0]
+def _users_geom(item_offsets, frame_offsets, frame_perm, excl):
+    """The sessions' geometry (frame_geometry) and the songs' bitmap as the C-ABI
+    reads them.  Returns (U, item_offsets, frame_offsets, frame_perm)."""
     item_offsets = _i64(item_offsets, "item_offsets").reshape(-1)
     frame_offsets = _i64(frame_offsets, "frame_offsets").reshape(-1)
     U = item_offsets.numel() - 1
@@ -571,12 +569,51 @@ def _users_args(X, C, item_offsets, frame_offsets, frame_perm, excl, out):
         frame_perm = _i64(frame_perm, "frame_perm").reshape(-1)
     if excl is not None:
         _check_excl(excl, frame_offsets.numel() - 1)
+    return U, item_offsets, frame_offsets, frame_perm
+
+
+def _users_args(X, C, item_offsets, frame_offsets, frame_perm, excl, out):
+    """The tail the users forms share: the geometry (_users_geom) and ``out``.
+    Returns (U, item_offsets, frame_offsets, frame_perm, out)."""
+    F = X.shape[0]
+    U, item_offsets, frame_offsets, frame_perm = _users_geom(item_offsets, frame_offsets, frame_perm, excl)
     if out is None:
         # rows of excluded songs are not written: a new tensor is zero there, the rule of frames_consensus
         out = (torch.zeros if excl is not None else torch.empty)((F, C), dtype=torch.float64, device=X.device)
     _on_gpu(out, "out")
     check_users_out(out, F, C)
     return U, item_offsets, frame_offsets, frame_perm, out
+
+
+def _gnb_users_model(X, theta, var, class_prior):
+    """U GaussianNB models over the frames X: theta / var [U, C, D], class_prior
+    [U, C] on the device.  Returns (F, D, U, C, theta, var, log_prior): the
+    log-prior is one ``log_f64`` over the flat priors."""
+    F, D = _check_X(X)
+    theta = _f64_dev(theta, X.device, "theta")
+    var = _f64_dev(var, X.device, "var")
+    if theta.dim() != 3 or theta.shape[2] != D or tuple(var.shape) != tuple(theta.shape):
+        raise ValueError(f"theta/var must be [U, C, {D}]")
+    Um, C = theta.shape[:2]
+    _on_gpu(class_prior, "class_prior")
+    if class_prior.numel() != Um * C:
+        raise ValueError(f"class_prior must be [U={Um}, C={C}]")
+    log_prior = log_f64(class_prior.to(device=X.device, dtype=torch.float64).reshape(-1).contiguous())
+    return F, D, Um, C, theta, var, log_prior
+
+
+def _sgd_users_model(X, coef, intercept):
+    """U SGDClassifier models over the frames X: coef [U, K, D], intercept [U, K];
+    K = C (OvR) or 1 (binary, C = 2).  Returns (F, D, U, C, K, coef, intercept)."""
+    F, D = _check_X(X)
+    coef = _f64_dev(coef, X.device, "coef")
+    if coef.dim() != 3 or coef.shape[2] != D:
+        raise ValueError(f"coef must be [U, K, {D}]")
+    Um, K = coef.shape[:2]
+    intercept = _f64_dev(intercept, X.device, "intercept").reshape(-1)
+    if intercept.numel() != Um * K:
+        raise ValueError(f"intercept must be [U={Um}, K={K}]")
+    return F, D, Um, 2 if K == 1 else K, K, coef, intercept
 
 
 def gnb_predict_proba_users(X, theta, var, class_prior, item_offsets, frame_offsets, frame_perm=None, excl=None,
@@ -595,19 +632,10 @@ def gnb_predict_proba_users(X, theta, var, class_prior, item_offsets, frame_offs
     skipped.  out: an optional float64 [F, C] view with unit column stride (a
     new tensor is zero-filled when ``excl`` is given).  Per row the bits are
     gnb_predict_proba's.  Nothing is synchronised."""
-    F, D = _check_X(X)
-    theta = _f64_dev(theta, X.device, "theta")
-    var = _f64_dev(var, X.device, "var")
-    if theta.dim() != 3 or theta.shape[2] != D or tuple(var.shape) != tuple(theta.shape):
-        raise ValueError(f"theta/var must be [U, C, {D}]")
-    Um, C = theta.shape[:2]
-    _on_gpu(class_prior, "class_prior")
-    if class_prior.numel() != Um * C:
-        raise ValueError(f"class_prior must be [U={Um}, C={C}]")
+    F, D, Um, C, theta, var, log_prior = _gnb_users_model(X, theta, var, class_prior)
     U, item_offsets, frame_offsets, frame_perm, out = _users_args(X, C, item_offsets, frame_offsets, frame_perm, excl, out)
     if U != Um:
         raise ValueError(f"item_offsets names {U} user(s), theta holds {Um} model(s)")
-    log_prior = log_f64(class_prior.to(device=X.device, dtype=torch.float64).reshape(-1).contiguous())
     call("ce_gnb_predict_proba_users", _p(X), F, D, X.stride(0), _p(theta), _p(var), _p(log_prior), C, U,
          _p(item_offsets), _p(frame_offsets), _p(frame_perm), _p(excl), _p(out), max(out.stride(0), C),
          _stream(X.device))
@@ -619,15 +647,7 @@ def sgd_predict_proba_users(X, coef, intercept, item_offsets, frame_offsets, fra
     [U, K, D], intercept [U, K]; K = C (OvR) or 1 (binary, C = 2).  Geometry,
     ``excl`` and ``out`` as gnb_predict_proba_users; per row the bits are
     sgd_predict_proba's."""
-    F, D = _check_X(X)
-    coef = _f64_dev(coef, X.device, "coef")
-    if coef.dim() != 3 or coef.shape[2] != D:
-        raise ValueError(f"coef must be [U, K, {D}]")
-    Um, K = coef.shape[:2]
-    intercept = _f64_dev(intercept, X.device, "intercept").reshape(-1)
-    if intercept.numel() != Um * K:
-        raise ValueError(f"intercept must be [U={Um}, K={K}]")
-    C = 2 if K == 1 else K
+    F, D, Um, C, K, coef, intercept = _sgd_users_model(X, coef, intercept)
     U, item_offsets, frame_offsets, frame_perm, out = _users_args(X, C, item_offsets, frame_offsets, frame_perm, excl, out)
     if U != Um:
         raise ValueError(f"item_offsets names {U} user(s), coef holds {Um} model(s)")
@@ -655,17 +675,9 @@ def _score_args(X, C, score_cols, U_models, item_offsets, frame_offsets, frame_p
     float64 [F, score_cols] of NaN where asked for -- what a row that is not
     counted keeps."""
     F = X.shape[0]
-    item_offsets = _i64(item_offsets, "item_offsets").reshape(-1)
-    frame_offsets = _i64(frame_offsets, "frame_offsets").reshape(-1)
-    U = item_offsets.numel() - 1
-    if U < 1 or frame_offsets.numel() < 1:
-        raise ValueError("item_offsets must hold U + 1 >= 2 entries and frame_offsets total_items + 1 >= 1")
+    U, item_offsets, frame_offsets, frame_perm = _users_geom(item_offsets, frame_offsets, frame_perm, excl)
     if U != U_models:
         raise ValueError(f"item_offsets names {U} user(s), the member holds {U_models} model(s)")
-    if frame_perm is not None:
-        frame_perm = _i64(frame_perm, "frame_perm").reshape(-1)
-    if excl is not None:
-        _check_excl(excl, frame_offsets.numel() - 1)
     y = _labels_i32(y, F)
     cm = torch.empty((U, C, C), dtype=torch.int64, device=X.device)
     pred = torch.full((F,), -1, dtype=torch.int32, device=X.device) if return_pred else None
@@ -687,18 +699,9 @@ def gnb_score_users(X, theta, var, class_prior, item_offsets, frame_offsets, y, 
     excluded or that no song owns is not counted.  Returns (cm int64 [U, C, C],
     pred int32 [F] or None, scores f64 [F, C] or None); rows not counted keep
     -1 in pred and NaN in scores.  Nothing is synchronised."""
-    F, D = _check_X(X)
-    theta = _f64_dev(theta, X.device, "theta")
-    var = _f64_dev(var, X.device, "var")
-    if theta.dim() != 3 or theta.shape[2] != D or tuple(var.shape) != tuple(theta.shape):
-        raise ValueError(f"theta/var must be [U, C, {D}]")
-    Um, C = theta.shape[:2]
-    _on_gpu(class_prior, "class_prior")
-    if class_prior.numel() != Um * C:
-        raise ValueError(f"class_prior must be [U={Um}, C={C}]")
+    F, D, Um, C, theta, var, log_prior = _gnb_users_model(X, theta, var, class_prior)
     U, item_offsets, frame_offsets, frame_perm, y, cm, pred, scores = _score_args(
         X, C, C, Um, item_offsets, frame_offsets, frame_perm, excl, y, return_pred, return_scores)
-    log_prior = log_f64(class_prior.to(device=X.device, dtype=torch.float64).reshape(-1).contiguous())
     call("ce_gnb_score_users", _p(X), F, D, X.stride(0), _p(theta), _p(var), _p(log_prior), C, U, _p(item_offsets),
          _p(frame_offsets), _p(frame_perm), _p(excl), _p(y), _p(cm), _p(pred), _p(scores), C, _stream(X.device))
     return cm, pred, scores
@@ -711,15 +714,7 @@ def sgd_score_users(X, coef, intercept, item_offsets, frame_offsets, y, frame_pe
     values) or 1 (binary, C = 2: decision > 0 is class 1).  The decision values
     are the ones sgd_predict_proba_users feeds to expit, bit for bit; scores is
     [F, K]."""
-    F, D = _check_X(X)
-    coef = _f64_dev(coef, X.device, "coef")
-    if coef.dim() != 3 or coef.shape[2] != D:
-        raise ValueError(f"coef must be [U, K, {D}]")
-    Um, K = coef.shape[:2]
-    intercept = _f64_dev(intercept, X.device, "intercept").reshape(-1)
-    if intercept.numel() != Um * K:
-        raise ValueError(f"intercept must be [U={Um}, K={K}]")
-    C = 2 if K == 1 else K
+    F, D, Um, C, K, coef, intercept = _sgd_users_model(X, coef, intercept)
     U, item_offsets, frame_offsets, frame_perm, y, cm, pred, scores = _score_args(
         X, C, K, Um, item_offsets, frame_offsets, frame_perm, excl, y, return_pred, return_scores)
     call("ce_sgd_score_users", _p(X), F, D, X.stride(0), _p(coef), _p(intercept), K, C, U, _p(item_offsets),

@@ -92,7 +92,7 @@ static inline int with_wide_v(const CommArgs& a, F&& f) {
     return CE_EUNSUPPORTED;
 }
 
-// ---- member inference dispatch (ce_members.hpp, ce_members_users.hpp) --------
+// ---- member inference dispatch (ce_members.hpp, ce_members_users.hpp, ce_members_score.hpp) ----
 // features per lane of the 8-lanes-per-frame kernels: ceil(D / 8), rounded up to a multiple of 8
 template <class F>
 static inline int with_nx(int D, F&& f) {
@@ -125,4 +125,21 @@ static inline int resident_grid(K kernel, size_t dyn_lds, int cap) {
     (void)hipGetLastError();
     const int g = per_cu * device_cus();
     return g < cap ? g : cap;
+}
+
+// The users forms (ce_members_users.hip, ce_members_score.hip): every block
+// resident at once, each with an equal share of the positions: at least 128 of
+// them (4 passes of the block), so a restage is amortised.  F bounds the
+// positions a well-formed geometry names; the kernel divides the real count,
+// which only the device knows, among the blocks launched.
+template <class K>
+static inline int users_grid(K kern, size_t lds, int64_t F) {
+    return resident_grid(kern, lds, (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(F, 128), 1 << 20)));
+}
+
+// What every users entry point checks of its geometry.
+static inline int check_users_geom(int32_t U, const int64_t* item_offsets, const int64_t* frame_offsets) {
+    if (U < 1) return fail(CE_EINVAL, "U=%d users: at least one", U);
+    if (!item_offsets || !frame_offsets) return fail(CE_EINVAL, "null offsets");
+    return CE_OK;
 }

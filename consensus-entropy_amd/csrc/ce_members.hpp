@@ -160,6 +160,81 @@ __device__ __forceinline__ double group_sum(const double (&t)[NX], const PwPlan&
         return group_pairwise<NX>(t, pl);
 }
 
+// ---- the kernels and what they share -------------------------------------------
+// One model for all rows: this file.  One model per user, probabilities or
+// scores: ce_members_users.hpp and ce_members_score.hpp.  The 8-lane kernels of
+// all three files stage, form the jll and finish through gnb_stage8, gnb_jll8
+// and gnb_proba8, and SGD's through sgd_decision8 / sgd_decision / expit /
+// sgd_store, below.  The 8-lane x[] load and the whole 260 form are stated in
+// the one-model kernel and again in the users kernels; the tests hold the two
+// statements to the same bits.
+
+// GaussianNB, 8 lanes per frame: one model (at theta / var) into the LDS tables
+// th, vr, rv [C][D], then hs1[c] = -0.5 * np.sum(np.log(2 pi var_c)), group c
+// computing class c.  Every thread of the block calls it, between the caller's barriers.
+template <int NX, int DF>
+__device__ __forceinline__ void gnb_stage8(double* th, double* vr, double* rv, double* hs1, const double* theta,
+                                           const double* var, int C, int D, const PwPlan& pl) {
+    for (int t = threadIdx.x; t < C * D; t += blockDim.x) {
+        th[t] = theta[t];
+        vr[t] = var[t];
+        rv[t] = 1.0 / var[t];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, j = lane & 7, g = lane >> 3, w = threadIdx.x >> 6;
+    if (w * 8 < C) {  // wave-uniform: the waves holding groups 0..C-1
+        const int gid = w * 8 + g, c = gid < C ? gid : 0;
+        double t[NX];
+#pragma unroll
+        for (int m = 0; m < NX; ++m) {
+            const int f = 8 * m + j;
+            t[m] = f < D ? glog(2. * M_PI * vr[c * D + f]) : 0.0;
+        }
+        const double s1 = group_sum<NX, DF>(t, pl);
+        if (gid < C && j == 0) hs1[gid] = -0.5 * s1;
+    }
+}
+
+// predict_proba from the jll: p_c = exp(jll_c - logsumexp(jll)); lane j < C of an active frame stores class j.
+__device__ __forceinline__ void gnb_proba8(const double (&jll)[kMaxMemberC], int C, bool act, double* out, int64_t ldo,
+                                           int64_t row) {
+    const int lane = threadIdx.x & 63, j = lane & 7;
+    double mx = jll[0];
+    for (int c = 1; c < C; ++c) mx = jll[c] > mx ? jll[c] : mx;
+    if (!__builtin_isfinite(mx)) mx = 0.0;
+    double s = -0.0;
+    for (int c = 0; c < C; ++c) s += gexp(jll[c] - mx);
+    const double lse = glog(0.0 + s) + mx;
+    if (act && j < C) {
+        double v = 0.0;
+        for (int c = 0; c < C; ++c)
+            if (c == j) v = gexp(jll[c] - lse);
+        out[row * ldo + j] = v;
+    }
+}
+
+// One frame's joint log-likelihood from its x[] and the staged model (th, vr,
+// rv [C][D], hs1 [C]); lp: the model's log-prior.
+template <int NX, int DF>
+__device__ __forceinline__ void gnb_jll8(double (&jll)[kMaxMemberC], const double (&x)[NX], const double* th,
+                                         const double* vr, const double* rv, const double* hs1, const double* lp, int C,
+                                         int D, const PwPlan& pl) {
+    const int lane = threadIdx.x & 63, j = lane & 7;
+    for (int c = 0; c < C; ++c) {
+        double t[NX];
+#pragma unroll
+        for (int m = 0; m < NX; ++m) {
+            const int f = 8 * m + j, fc = f < D ? f : 0;
+            const double d = x[m] - th[c * D + fc];
+            t[m] = f < D ? div_by_recip(d * d, vr[c * D + fc], rv[c * D + fc]) : 0.0;
+        }
+        const double s2 = group_sum<NX, DF>(t, pl);
+        double n_ij = hs1[c];
+        n_ij -= 0.5 * s2;
+        jll[c] = lp[c] + n_ij;
+    }
+}
+
 // GaussianNB, 8 lanes per frame.  LDS: theta, var, 1/var [C][D] doubles, and
 // the per-class -0.5 * np.sum(np.log(2 pi var_c)) (group c computes class c once).
 template <int NX, int DF>  // DF: the feature count when fixed at compile time (0: a.D, runtime plan)
@@ -169,24 +244,8 @@ __global__ __launch_bounds__(256) void k_gnb_proba8(GnbArgs a, PwPlan pl) {
     double* th = msm;
     double* vr = msm + (int64_t)a.C * a.D;
     double* rv = msm + (int64_t)2 * a.C * a.D;
-    for (int t = threadIdx.x; t < a.C * a.D; t += blockDim.x) {
-        th[t] = a.theta[t];
-        vr[t] = a.var[t];
-        rv[t] = 1.0 / a.var[t];
-    }
-    __syncthreads();
+    gnb_stage8<NX, DF>(th, vr, rv, hs1, a.theta, a.var, a.C, a.D, pl);
     const int lane = threadIdx.x & 63, j = lane & 7, g = lane >> 3, w = threadIdx.x >> 6;
-    if (w * 8 < a.C) {  // wave-uniform: the waves holding groups 0..C-1
-        const int gid = w * 8 + g, c = gid < a.C ? gid : 0;
-        double t[NX];
-#pragma unroll
-        for (int m = 0; m < NX; ++m) {
-            const int f = 8 * m + j;
-            t[m] = f < a.D ? glog(2. * M_PI * vr[c * a.D + f]) : 0.0;
-        }
-        const double s1 = group_sum<NX, DF>(t, pl);
-        if (gid < a.C && j == 0) hs1[gid] = -0.5 * s1;
-    }
     __syncthreads();
     const int64_t step = (int64_t)gridDim.x * 32;
     for (int64_t f0 = ((int64_t)blockIdx.x * 4 + w) * 8; f0 < a.F; f0 += step) {
@@ -199,36 +258,13 @@ __global__ __launch_bounds__(256) void k_gnb_proba8(GnbArgs a, PwPlan pl) {
             x[m] = f < a.D ? a.X[frc * a.ld + f] : 0.0;
         }
         double jll[kMaxMemberC];
-        for (int c = 0; c < a.C; ++c) {
-            double t[NX];
-#pragma unroll
-            for (int m = 0; m < NX; ++m) {
-                const int f = 8 * m + j, fc = f < a.D ? f : 0;
-                const double d = x[m] - th[c * a.D + fc];
-                t[m] = f < a.D ? div_by_recip(d * d, vr[c * a.D + fc], rv[c * a.D + fc]) : 0.0;
-            }
-            const double s2 = group_sum<NX, DF>(t, pl);
-            double n_ij = hs1[c];
-            n_ij -= 0.5 * s2;
-            jll[c] = a.log_prior[c] + n_ij;
-        }
-        double mx = jll[0];
-        for (int c = 1; c < a.C; ++c) mx = jll[c] > mx ? jll[c] : mx;
-        if (!__builtin_isfinite(mx)) mx = 0.0;
-        double s = -0.0;
-        for (int c = 0; c < a.C; ++c) s += gexp(jll[c] - mx);
-        const double lse = glog(0.0 + s) + mx;
-        if (fr < a.F && j < a.C) {
-            double v = 0.0;
-            for (int c = 0; c < a.C; ++c)
-                if (c == j) v = gexp(jll[c] - lse);
-            a.out[fr * a.ldo + j] = v;
-        }
+        gnb_jll8<NX, DF>(jll, x, th, vr, rv, hs1, a.log_prior, a.C, a.D, pl);
+        gnb_proba8(jll, a.C, fr < a.F, a.out, a.ldo, fr);
     }
 }
 
 // GaussianNB for the reference's shape (D = 260 features, KC = C classes),
-// feature-streamed: k_gnb_proba8 holds a frame group's 33 feature values AND
+// feature-streamed: the 8-lane form holds a frame group's 33 feature values AND
 // one class's 33 terms in registers before each pairwise sum, and issues the
 // next group's loads only when the group is done.  Here the column loop is
 // outermost: x[m] feeds the KC classes' terms at once, and each term goes
@@ -241,14 +277,16 @@ __global__ __launch_bounds__(256) void k_gnb_proba8(GnbArgs a, PwPlan pl) {
 // butterfly (((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) in every lane of the group),
 // the 4 tail features 256..259 are added in order, and the row sum is
 // 0.0 + (L0 + (L1 + L2)) -- the same operations in the same order as
-// k_gnb_proba8 and numpy.  LDS: {theta, 1/var} pairs (one ds_read_b128) and
-// var, per class and feature.
+// k_gnb_proba8 and numpy.  LDS: {theta, 1/var} pairs (one ds_read_b128) and var,
+// per class and feature.
+constexpr int kD260 = 260, kNX260 = 33;
+static_assert(pw_plan(kD260).nleaves == 3 && pw_plan(kD260).lstart[1] == 128 && pw_plan(kD260).lstart[2] == 192 &&
+                  pw_plan(kD260).llen[2] == 68,
+              "the leaf layout the 260 kernels hard-code");
+
 template <int KC, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_gnb_stream260(GnbArgs a) {
-    constexpr int D = 260, NX = 33;
-    static_assert(pw_plan(D).nleaves == 3 && pw_plan(D).lstart[1] == 128 && pw_plan(D).lstart[2] == 192 &&
-                      pw_plan(D).llen[2] == 68,
-                  "the leaf layout this kernel hard-codes");
+    constexpr int D = kD260, NX = kNX260;
     __shared__ __attribute__((aligned(16))) f64x2 tr[KC * D];  // {theta, RN(1/var)}
     __shared__ double vr[KC * D];
     __shared__ double hs1[KC];
@@ -374,14 +412,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     }
 }
 
-// Lane j's partial dot product -> the group's d (butterfly) -> expit(d + b).
-__device__ __forceinline__ double sgd_expit(double d, double b) {
+// SGD's decision value: the group's butterfly of the lanes' partial dot
+// products d, then the intercept b.  The score kernels compare these; the
+// proba kernels feed them to expit.
+__device__ __forceinline__ double sgd_decision(double d, double b) {
     d = d + __shfl_xor(d, 1);
     d = d + __shfl_xor(d, 2);
     d = d + __shfl_xor(d, 4);
     d += b;
-    return 1.0 / (1.0 + gexp(-d));  // scipy.special.expit
+    return d;
 }
+
+// Class c's decision value from the frame's x[] (load8): lane j's fma chain
+// over its features (cf: coef [K][D]), then sgd_decision with icpt[c].
+template <int NX>
+__device__ __forceinline__ double sgd_decision8(const double (&x)[NX], const double* cf, const double* icpt, int c, int D) {
+    const int lane = threadIdx.x & 63, j = lane & 7;
+    double d = 0.0;
+#pragma unroll
+    for (int m = 0; m < NX; ++m) {
+        const int f = 8 * m + j;
+        if (f < D) d = fma(x[m], cf[c * D + f], d);
+    }
+    return sgd_decision(d, icpt[c]);
+}
+
+// scipy.special.expit of a decision value
+__device__ __forceinline__ double expit(double d) { return 1.0 / (1.0 + gexp(-d)); }
+
+// Lane j's partial dot product -> the decision value -> its expit.
+__device__ __forceinline__ double sgd_expit(double d, double b) { return expit(sgd_decision(d, b)); }
 
 template <int KR>
 __device__ __forceinline__ void sgd_store(const SgdArgs& a, double (&p)[KR], int K, int64_t fr, int j);
@@ -404,15 +464,7 @@ __global__ __launch_bounds__(256) void k_sgd_proba8(SgdArgs a) {
             x[m] = f < a.D ? a.X[frc * a.ld + f] : 0.0;
         }
         double p[kMaxMemberC];
-        for (int c = 0; c < a.K; ++c) {
-            double d = 0.0;
-#pragma unroll
-            for (int m = 0; m < NX; ++m) {
-                const int f = 8 * m + j;
-                if (f < a.D) d = fma(x[m], msm[c * a.D + f], d);
-            }
-            p[c] = sgd_expit(d, a.intercept[c]);
-        }
+        for (int c = 0; c < a.K; ++c) p[c] = expit(sgd_decision8(x, msm, a.intercept, c, a.D));
         sgd_store(a, p, a.K, fr, j);
     }
 }

@@ -8,19 +8,12 @@
 
 using namespace ce;
 
-// As ce_members_users.hip: every block resident at once, each with an equal
-// share of the positions, at least 128 of them.
-template <class K>
-static int users_grid(K kern, size_t lds, int64_t F) {
-    return resident_grid(kern, lds, (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(F, 128), 1 << 20)));
-}
-
 // What the two score entry points check alike, after their own shapes; cm is zero-filled here.
 static int score_common(const char* what, int64_t F, int32_t C, int32_t U, const int64_t* item_offsets,
                         const int64_t* frame_offsets, const int32_t* y, int64_t* cm, const double* scores,
                         int64_t ld_scores, int32_t score_cols, hipStream_t st) {
-    if (U < 1) return fail(CE_EINVAL, "U=%d users: at least one", U);
-    if (!item_offsets || !frame_offsets) return fail(CE_EINVAL, "null offsets");
+    const int rc = check_users_geom(U, item_offsets, frame_offsets);
+    if (rc) return rc;
     if (!cm || (F > 0 && !y)) return fail(CE_EINVAL, "null y or cm");
     if (scores && ld_scores < score_cols)
         return fail(CE_EINVAL, "ld_scores=%lld below the %d score column(s)", (long long)ld_scores, score_cols);

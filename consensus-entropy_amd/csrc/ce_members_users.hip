@@ -6,21 +6,6 @@
 
 using namespace ce;
 
-// Every block resident at once, each with an equal share of the positions: at
-// least 128 of them (4 passes of the block), so a restage is amortised.  F
-// bounds the positions a well-formed geometry names; the kernel divides the
-// real count, which only the device knows, among the blocks launched.
-template <class K>
-static int users_grid(K kern, size_t lds, int64_t F) {
-    return resident_grid(kern, lds, (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(F, 128), 1 << 20)));
-}
-
-static int check_geom(int32_t U, const int64_t* item_offsets, const int64_t* frame_offsets) {
-    if (U < 1) return fail(CE_EINVAL, "U=%d users: at least one", U);
-    if (!item_offsets || !frame_offsets) return fail(CE_EINVAL, "null offsets");
-    return CE_OK;
-}
-
 extern "C" int ce_gnb_predict_proba_users(const double* X, int64_t F, int32_t D, int64_t ld, const double* theta,
                                           const double* var, const double* log_prior, int32_t C, int32_t U,
                                           const int64_t* item_offsets, const int64_t* frame_offsets,
@@ -28,7 +13,7 @@ extern "C" int ce_gnb_predict_proba_users(const double* X, int64_t F, int32_t D,
                                           int64_t ld_out, ce_stream_t stream) {
     if (F < 0 || D < 1 || D > kMaxFeat || ld < D || C < 1 || C > kMaxMemberC || ld_out < C)
         return fail(CE_EINVAL, "bad GaussianNB shapes F=%lld D=%d C=%d", (long long)F, D, C);
-    int rc = check_geom(U, item_offsets, frame_offsets);
+    int rc = check_users_geom(U, item_offsets, frame_offsets);
     if (rc) return rc;
     if ((F > 0 && (!X || !out)) || !theta || !var || !log_prior) return fail(CE_EINVAL, "null pointer");
     if (D < 8) return fail(CE_EUNSUPPORTED, "GaussianNB needs D >= 8 features (got %d)", D);  // as ce_gnb_predict_proba
@@ -63,7 +48,7 @@ extern "C" int ce_sgd_predict_proba_users(const double* X, int64_t F, int32_t D,
     if (F < 0 || D < 1 || D > kMaxFeat || ld < D || C < 2 || C > kMaxMemberC || ld_out < C ||
         !(K == C || (K == 1 && C == 2)))
         return fail(CE_EINVAL, "bad SGD shapes F=%lld D=%d K=%d C=%d", (long long)F, D, K, C);
-    int rc = check_geom(U, item_offsets, frame_offsets);
+    int rc = check_users_geom(U, item_offsets, frame_offsets);
     if (rc) return rc;
     if ((F > 0 && (!X || !out)) || !coef || !intercept) return fail(CE_EINVAL, "null pointer");
     if (F == 0) return CE_OK;

@@ -16,8 +16,16 @@
 // a time, restaging at a block-wide barrier when the share crosses into the
 // next user.  A wave's 8 frames are 8 consecutive positions of ONE user.
 //
-// Per frame the arithmetic is k_gnb_proba8's / k_sgd_proba8's (ce_members.hpp),
-// through the same helpers, so the output is theirs bit for bit.
+// The GaussianNB 260 form and SGD are one body each: the walk with that
+// family's staging and per-frame values, templated on a finish that says what
+// is done with the values.  Their proba kernels here and their score kernels in
+// ce_members_score.hpp are the same body with two finishes, so the scores are
+// the proba kernels' intermediates bit for bit by construction.  The general
+// GaussianNB form (k_gnb_proba_users, k_gnb_score_users) is two kernels.
+// Against the one-model kernels (ce_members.hpp): the 8-lane staging, jll and
+// proba finish and SGD's decision value are the same functions; the 8-lane
+// x[] load and the 260 form restate the one-model kernels' text, and the tests
+// hold the two to the same bits.
 //
 // A position whose row is outside [0, F) is neither read nor written; with an
 // exclusion bitmap over the stacked songs, the rows of an excluded song are
@@ -112,79 +120,19 @@ __device__ __forceinline__ void users_walk(const UsersGeom& ug, int64_t F, Stage
     });
 }
 
-// GaussianNB, 8 lanes per frame, one model per user: a.theta / a.var [U, C, D],
-// a.log_prior [U, C].  LDS as k_gnb_proba8: theta, var, 1/var [C][D] and the
-// per-class -0.5 * np.sum(np.log(2 pi var_c)) of the staged user.
-template <int NX, int DF>  // DF: the feature count when fixed at compile time (0: a.D, runtime plan)
-__global__ __launch_bounds__(256) void k_gnb_proba_users(GnbArgs a, UsersGeom ug, PwPlan pl) {
-    extern __shared__ __attribute__((aligned(16))) double msm[];
-    __shared__ double hs1[kMaxMemberC];
-    const int CD = a.C * a.D;
-    double* th = msm;
-    double* vr = msm + CD;
-    double* rv = msm + 2 * CD;
-    const int lane = threadIdx.x & 63, j = lane & 7, g = lane >> 3, w = threadIdx.x >> 6;
-    const double* lp = a.log_prior;
-    auto stage = [&](int u) {
-        __syncthreads();  // the previous user's frames are done with the tables
-        const double* tu = a.theta + (int64_t)u * CD;
-        const double* vu = a.var + (int64_t)u * CD;
-        for (int t = threadIdx.x; t < CD; t += blockDim.x) {
-            th[t] = tu[t];
-            vr[t] = vu[t];
-            rv[t] = 1.0 / vu[t];
-        }
-        __syncthreads();
-        if (w * 8 < a.C) {  // wave-uniform: the waves holding groups 0..C-1
-            const int gid = w * 8 + g, c = gid < a.C ? gid : 0;
-            double t[NX];
-#pragma unroll
-            for (int m = 0; m < NX; ++m) {
-                const int f = 8 * m + j;
-                t[m] = f < a.D ? glog(2. * M_PI * vr[c * a.D + f]) : 0.0;
-            }
-            const double s1 = group_sum<NX, DF>(t, pl);
-            if (gid < a.C && j == 0) hs1[gid] = -0.5 * s1;
-        }
-        lp = a.log_prior + (int64_t)u * a.C;
-        __syncthreads();
-    };
-    auto frames = [&](bool act, int64_t row) {
-        double x[NX];
-#pragma unroll
-        for (int m = 0; m < NX; ++m) {
-            const int f = 8 * m + j;
-            x[m] = (act && f < a.D) ? a.X[row * a.ld + f] : 0.0;
-        }
-        double jll[kMaxMemberC];
-        for (int c = 0; c < a.C; ++c) {
-            double t[NX];
-#pragma unroll
-            for (int m = 0; m < NX; ++m) {
-                const int f = 8 * m + j, fc = f < a.D ? f : 0;
-                const double d = x[m] - th[c * a.D + fc];
-                t[m] = f < a.D ? div_by_recip(d * d, vr[c * a.D + fc], rv[c * a.D + fc]) : 0.0;
-            }
-            const double s2 = group_sum<NX, DF>(t, pl);
-            double n_ij = hs1[c];
-            n_ij -= 0.5 * s2;
-            jll[c] = lp[c] + n_ij;
-        }
-        double mx = jll[0];
-        for (int c = 1; c < a.C; ++c) mx = jll[c] > mx ? jll[c] : mx;
-        if (!__builtin_isfinite(mx)) mx = 0.0;
-        double s = -0.0;
-        for (int c = 0; c < a.C; ++c) s += gexp(jll[c] - mx);
-        const double lse = glog(0.0 + s) + mx;
-        if (act && j < a.C) {
-            double v = 0.0;
-            for (int c = 0; c < a.C; ++c)
-                if (c == j) v = gexp(jll[c] - lse);
-            a.out[row * a.ldo + j] = v;
-        }
-    };
-    users_walk(ug, a.F, stage, frames);
-}
+// ---- the kernels' bodies -------------------------------------------------------
+// A body is the walk with one family's staging and per-frame values; what is
+// done with the values is its finish `fin`, a small struct of three hooks:
+//   fin.restage(u)             the tables are about to change hands to user u (every
+//                              thread, behind the barrier that ends the previous run)
+//   fin.frame(s, n, act, row)  one frame's n values s[] -- GaussianNB: the jll, SGD:
+//                              the decision values -- in every lane of its 8-lane group
+//   fin.done()                 after the walk (every thread of the block)
+// SGD's finish has a fourth, fin.value(d): what of a decision value goes into
+// s[] -- its expit (proba) or itself (score).  It is taken class by class
+// inside the loop, as k_sgd_proba8 does: a frame() that applies expit to the
+// whole s[] afterwards compiles to another register count (20 VGPRs off) for
+// every k_sgd_proba_users<NX>.
 
 // GaussianNB for the reference's shape (D = 260, KC = C classes), one model per
 // user: k_gnb_stream260's feature-streamed frame loop (ce_members.hpp -- the
@@ -193,14 +141,10 @@ __global__ __launch_bounds__(256) void k_gnb_proba_users(GnbArgs a, UsersGeom ug
 // inside a run of one user.  The next group is the wave's next one WITH a frame
 // to compute (excluded groups are stepped over before anything is loaded); past
 // the run's end the refill reads row 0, and the first group of the next run
-// loads afresh after the restage.  The same operations in the same order as
-// k_gnb_stream260, so the same bits.
-template <int KC, int WPE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_gnb_users260(GnbArgs a, UsersGeom ug) {
-    constexpr int D = 260, NX = 33;
-    static_assert(pw_plan(D).nleaves == 3 && pw_plan(D).lstart[1] == 128 && pw_plan(D).lstart[2] == 192 &&
-                      pw_plan(D).llen[2] == 68,
-                  "the leaf layout this kernel hard-codes");
+// loads afresh after the restage.
+template <int KC, int WPE, class Fin>
+__device__ __forceinline__ void gnb_users260(const GnbArgs& a, const UsersGeom& ug, Fin& fin) {
+    constexpr int D = kD260, NX = kNX260;
     __shared__ __attribute__((aligned(16))) f64x2 tr[KC * D];  // {theta, RN(1/var)}
     __shared__ double vr[KC * D];
     __shared__ double lgv[KC * D];  // log(2 pi var): every thread computes its share, wave 0 sums them
@@ -211,6 +155,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: the group positions stay scalar
     auto stage = [&](int u) {
         __syncthreads();  // the previous user's frames are done with the tables
+        fin.restage(u);
         const double* tu = a.theta + (int64_t)u * KC * D;
         const double* vu = a.var + (int64_t)u * KC * D;
 #pragma unroll 1  // one log live at a time: the run's first group (x) is in registers across the restage
@@ -222,7 +167,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         }
         if (threadIdx.x < KC) lpr[threadIdx.x] = a.log_prior[(int64_t)u * KC + threadIdx.x];
         __syncthreads();
-        if (w == 0) {  // -0.5 * np.sum(np.log(2 pi var_c)): group c < KC sums class c, leaf by leaf
+        if (w == 0) {  // -0.5 * np.sum(np.log(2 pi var_c)): group c < KC sums class c
             const int c = g < KC ? g : 0;
             const double* v = lgv + c * D + j;
             auto lg = [&](int m) { return v[8 * m]; };
@@ -324,44 +269,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                 n_ij -= 0.5 * s2;
                 jll[c] = lpr[c] + n_ij;
             }
-            double mx = jll[0];
-#pragma unroll
-            for (int c = 1; c < KC; ++c) mx = jll[c] > mx ? jll[c] : mx;
-            if (!__builtin_isfinite(mx)) mx = 0.0;
-            double s = -0.0;
-#pragma unroll
-            for (int c = 0; c < KC; ++c) {
-                s += gexp(jll[c] - mx);
-                asm volatile("" : "+v"(s));
-            }
-            const double lse = glog(0.0 + s) + mx;
-            if (act && j < KC) {
-                double jl = jll[0];
-#pragma unroll
-                for (int c = 1; c < KC; ++c)
-                    if (c == j) jl = jll[c];
-                a.out[row * a.ldo + j] = gexp(jl - lse);  // lane j's class only
-            }
+            fin.frame(jll, KC, act, row);
             q0 = qn, act = actn, row = rown;
         }
     };
     users_runs(ug, pre, stage, run);
+    fin.done();
 }
 
 // SGDClassifier(loss='log'), 8 lanes per frame, one model per user: a.coef
 // [U, K, D], a.intercept [U, K].  LDS: the staged user's coef [K][D], then its
 // intercept [K].
-template <int NX>
-__global__ __launch_bounds__(256) void k_sgd_proba_users(SgdArgs a, UsersGeom ug) {
+template <int NX, class Fin>
+__device__ __forceinline__ void sgd_users8(const SgdArgs& a, const UsersGeom& ug, Fin& fin) {
     extern __shared__ __attribute__((aligned(16))) double msm[];
     const int KD = a.K * a.D;
     double* ic = msm + KD;
     const int lane = threadIdx.x & 63, j = lane & 7;
     auto stage = [&](int u) {
         __syncthreads();  // the previous user's frames are done with the table
+        fin.restage(u);
         const double* cu = a.coef + (int64_t)u * KD;
         for (int t = threadIdx.x; t < KD; t += blockDim.x) msm[t] = cu[t];
-        if (threadIdx.x < a.K) ic[threadIdx.x] = a.intercept[(int64_t)u * a.K + threadIdx.x];
+        if ((int)threadIdx.x < a.K) ic[threadIdx.x] = a.intercept[(int64_t)u * a.K + threadIdx.x];
         __syncthreads();
     };
     auto frames = [&](bool act, int64_t row) {
@@ -371,19 +301,102 @@ __global__ __launch_bounds__(256) void k_sgd_proba_users(SgdArgs a, UsersGeom ug
             const int f = 8 * m + j;
             x[m] = (act && f < a.D) ? a.X[row * a.ld + f] : 0.0;
         }
-        double p[kMaxMemberC];
-        for (int c = 0; c < a.K; ++c) {
-            double d = 0.0;
-#pragma unroll
-            for (int m = 0; m < NX; ++m) {
-                const int f = 8 * m + j;
-                if (f < a.D) d = fma(x[m], msm[c * a.D + f], d);
-            }
-            p[c] = sgd_expit(d, ic[c]);
-        }
-        sgd_store(a, p, a.K, act ? row : a.F, j);  // row F: no store
+        double d[kMaxMemberC];
+        for (int c = 0; c < a.K; ++c) d[c] = fin.value(sgd_decision8(x, msm, ic, c, a.D));
+        fin.frame(d, a.K, act, row);
     };
     users_walk(ug, a.F, stage, frames);
+    fin.done();
+}
+
+// ---- the proba finishes and their kernels ---------------------------------------
+struct NoCounts {  // nothing to do at a restage or after the walk
+    __device__ __forceinline__ void restage(int) {}
+    __device__ __forceinline__ void done() {}
+};
+
+struct GnbProbaFin260 : NoCounts {
+    double* out;
+    int64_t ldo;
+    template <int KC>
+    __device__ __forceinline__ void frame(const double (&jll)[KC], int, bool act, int64_t row) {
+        const int j = threadIdx.x & 7;
+        double mx = jll[0];
+#pragma unroll
+        for (int c = 1; c < KC; ++c) mx = jll[c] > mx ? jll[c] : mx;
+        if (!__builtin_isfinite(mx)) mx = 0.0;
+        // one transcendental at a time, as in k_gnb_stream260
+        double s = -0.0;
+#pragma unroll
+        for (int c = 0; c < KC; ++c) {
+            s += gexp(jll[c] - mx);
+            asm volatile("" : "+v"(s));
+        }
+        const double lse = glog(0.0 + s) + mx;
+        if (act && j < KC) {
+            double jl = jll[0];
+#pragma unroll
+            for (int c = 1; c < KC; ++c)
+                if (c == j) jl = jll[c];
+            out[row * ldo + j] = gexp(jl - lse);  // lane j's class only
+        }
+    }
+};
+
+struct SgdProbaFin : NoCounts {
+    const SgdArgs& a;
+    __device__ __forceinline__ double value(double d) { return expit(d); }
+    __device__ __forceinline__ void frame(double (&d)[kMaxMemberC], int K, bool act, int64_t row) {
+        sgd_store(a, d, K, act ? row : a.F, threadIdx.x & 7);  // row F: no store
+    }
+};
+
+// The general GaussianNB form is not a body with a finish: k_gnb_proba_users here
+// and k_gnb_score_users (ce_members_score.hpp) are two kernels over the same
+// functions of ce_members.hpp (gnb_stage8, gnb_jll8).
+// GaussianNB, 8 lanes per frame, one model per user: a.theta / a.var [U, C, D],
+// a.log_prior [U, C].  LDS as k_gnb_proba8: theta, var, 1/var [C][D] and the
+// per-class -0.5 * np.sum(np.log(2 pi var_c)) of the staged user.
+template <int NX, int DF>  // DF: the feature count when fixed at compile time (0: a.D, runtime plan)
+__global__ __launch_bounds__(256) void k_gnb_proba_users(GnbArgs a, UsersGeom ug, PwPlan pl) {
+    extern __shared__ __attribute__((aligned(16))) double msm[];
+    __shared__ double hs1[kMaxMemberC];
+    const int CD = a.C * a.D;
+    double* th = msm;
+    double* vr = msm + CD;
+    double* rv = msm + 2 * CD;
+    const int lane = threadIdx.x & 63, j = lane & 7;
+    const double* lp = a.log_prior;
+    auto stage = [&](int u) {
+        __syncthreads();  // the previous user's frames are done with the tables
+        gnb_stage8<NX, DF>(th, vr, rv, hs1, a.theta + (int64_t)u * CD, a.var + (int64_t)u * CD, a.C, a.D, pl);
+        lp = a.log_prior + (int64_t)u * a.C;
+        __syncthreads();
+    };
+    auto frames = [&](bool act, int64_t row) {
+        double x[NX];
+#pragma unroll
+        for (int m = 0; m < NX; ++m) {
+            const int f = 8 * m + j;
+            x[m] = (act && f < a.D) ? a.X[row * a.ld + f] : 0.0;
+        }
+        double jll[kMaxMemberC];
+        gnb_jll8<NX, DF>(jll, x, th, vr, rv, hs1, lp, a.C, a.D, pl);
+        gnb_proba8(jll, a.C, act, a.out, a.ldo, row);
+    };
+    users_walk(ug, a.F, stage, frames);
+}
+
+template <int KC, int WPE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_gnb_users260(GnbArgs a, UsersGeom ug) {
+    GnbProbaFin260 fin{{}, a.out, a.ldo};
+    gnb_users260<KC, WPE>(a, ug, fin);
+}
+
+template <int NX>
+__global__ __launch_bounds__(256) void k_sgd_proba_users(SgdArgs a, UsersGeom ug) {
+    SgdProbaFin fin{{}, a};
+    sgd_users8<NX>(a, ug, fin);
 }
 
 }  // namespace ce

@@ -230,6 +230,30 @@ def test_one_user_over_several_blocks(ce, kind, D):
     assert cm[1].sum() == (counted & (pool.user == 1)).sum() > 4000
 
 
+@pytest.mark.parametrize("kind", ["gnb", "sgd"])
+def test_scores_against_the_one_model_entry_points(ce, kind):
+    """The score and the proba kernel of the 260 form and of SGD are one body, so
+    `check` compares only their finishes there.  Here the scores go through the
+    proba tail and must equal, in all 64 bits, the ONE-model entry point
+    (k_gnb_stream260 / k_sgd_span260: a text of their own) run per user.  Users
+    of 5, 0 and 70 positions: a boundary inside an 8-frame group, a user without
+    a frame, more than two 32-position passes; C = 4, D = ld = 260."""
+    rng = np.random.default_rng(14)
+    pool = Pool(rng, [[5], [], [30, 40]])
+    C, D = 4, 260
+    Xd = dev(rng.normal(0, 1, (pool.F, D)))
+    models = gnb_models(rng, pool.U, C, D) if kind == "gnb" else sgd_models(rng, pool.U, C, D)
+    y = rng.integers(0, C, pool.F).astype(np.int64)
+    _, _, scores = score(ce, kind, Xd, models, pool.geometry(), dev(y))
+    assert last_kernel(ce) == (STREAMED if kind == "gnb" else "ce::k_sgd_score_users<36>")
+    assert [int((pool.user == u).sum()) for u in range(pool.U)] == [5, 0, 70]
+    for u in (0, 2):
+        rows = pool.user == u
+        m = [dev(a[u]) for a in models]
+        one = (ce.ops.gnb_predict_proba if kind == "gnb" else ce.ops.sgd_predict_proba)(Xd, *m).cpu().numpy()
+        assert same_bits(proba_from_scores(kind, scores[rows], C), one[rows]), u
+
+
 # ---- 2. feature and class edges ---------------------------------------------------------
 @pytest.mark.parametrize("C", [2, 3, 4, 8])
 @pytest.mark.parametrize("D", [8, 9, 64, 260, 512])
