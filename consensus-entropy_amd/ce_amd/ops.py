@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import CE_BF16, CE_F32, CE_F64, call
+from .xgb import LANE_TABLE_DEPTH, XgbForest
 
 _DT = {torch.float32: CE_F32, torch.float64: CE_F64, torch.bfloat16: CE_BF16}
 LAYOUTS = ("MNC", "NMC")
@@ -1009,13 +1010,12 @@ def batch_rows(songs, frame_offsets, frame_perm=None, song_labels=None, item_off
 
 def xgb_predict_proba(X, forest, out=None, out_dtype=torch.float32):
     """XGBClassifier(...).predict_proba(X) on the device (xgboost 1.3.3
-    predictor restated in csrc/ce_xgb.hip; xgboost/sklearn.py:991-1029,
-    amg_test.py:435).  X [F, D] f32/f64 frames (cast to float32 like DMatrix,
-    NaN = missing); ``forest`` an ``ce_amd.xgb.XgbForest`` (or its JSON).
-    Returns [F, C] ``out_dtype`` (float32 = what xgboost returns; float64 = its
-    exact upcast, ready for a committee stack)."""
-    from .xgb import XgbForest
-
+    predictor restated in csrc/ce_xgb.hpp and ce_xgb_walk.hpp;
+    xgboost/sklearn.py:991-1029, amg_test.py:435).  X [F, D] f32/f64 frames
+    (cast to float32 like DMatrix, NaN = missing); ``forest`` an
+    ``ce_amd.xgb.XgbForest`` (or its JSON).  Returns [F, C] ``out_dtype``
+    (float32 = what xgboost returns; float64 = its exact upcast, ready for a
+    committee stack)."""
     F, D = _check_X(X, (torch.float32, torch.float64))
     if not isinstance(forest, XgbForest):
         forest = XgbForest.from_json(forest)
@@ -1036,9 +1036,6 @@ def xgb_predict_proba(X, forest, out=None, out_dtype=torch.float32):
         call("ce_xgb_predict_proba", _p(X), _DT[X.dtype], F, D, X.stride(0), _p(nodes), _p(leaves), _p(goff), G,
              depth, float(forest.base_margin), C, _p(out), _DT[out.dtype], out.stride(0), _stream(X.device))
     return out
-
-
-LANE_TABLE_DEPTH = 5  # csrc/ce_xgb.hip kXgbLaneDepth: 2^(d+1) heap entries fit one wave
 
 
 def _check_q(q):

@@ -27,9 +27,11 @@ import os
 
 import numpy as np
 
-MAX_DEPTH = 10
-MAX_FEATURES = 512
-MAX_GROUPS = 8
+# the member's limits, each mirroring a constant of csrc/ce_xgb.hpp
+MAX_DEPTH = 10        # kXgbMaxDepth: packed perfect trees of at most 2^10 leaves
+LANE_TABLE_DEPTH = 5  # kXgbLaneDepth: 2^(d+1) heap entries fit one wave (prebuilt lane tables)
+MAX_FEATURES = 512    # kXgbMaxFeat: the LDS tile's columns
+MAX_GROUPS = 8        # kXgbMaxGroups: margin chains (waves) per block
 
 _libm = None
 

@@ -407,7 +407,8 @@ int ce_f1_weighted_users(const int64_t *cm, int32_t U, int32_t C, double *f1, do
 /*
  * XGBClassifier.predict_proba on the device (the
  * 'classifier_xgb' member; amg_test.py:435/:467 -> xgboost/sklearn.py:991-1029
- * -> libxgboost 1.3.3 CPU predictor, restated in csrc/ce_xgb.hip).
+ * -> libxgboost 1.3.3 CPU predictor, restated in csrc/ce_xgb.hpp and
+ * csrc/ce_xgb_walk.hpp; csrc/ce_xgb.hip holds these entries).
  * X [F, D] (x_dt F32|F64, row stride ld; cast to float32 like DMatrix, NaN =
  * missing), D <= 512.  The forest is packed by ce_amd.xgb.XgbForest: every tree
  * padded to a perfect tree of depth `depth` (<= 10), stored group-major --

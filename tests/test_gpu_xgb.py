@@ -167,11 +167,12 @@ def test_xgb_member_in_committee(ce):
 @pytest.mark.parametrize("name", ["reference_member", "ragged_tail", "three_class", "binary", "stumps",
                                   "leaves_only", "odd_features_d5", "d200_chunks4", "d400_chunks8"])
 def test_xgb_lane_paths_agree(ce, name, nan):
-    """The three walks of a depth <= 5 forest through the C-ABI directly:
-    ce_xgb_predict_proba (per-tile tables built on the fly) and
+    """The two walks of a depth <= 5 forest that the C-ABI reaches, called
+    directly: ce_xgb_predict_proba (per-tile tables built on the fly) and
     ce_xgb_predict_proba_lanes over the ce_xgb_lane_table tables (what
     ops.xgb_predict_proba runs) -- bit-identical to each other and to the
-    restated predictor; the lane ABI refuses a deeper forest."""
+    restated predictor; the lane ABI refuses a deeper forest.  (The third
+    walk, the perfect-tree gathers, runs only at depth > 5.)"""
     from ce_amd import _lib
     from ce_amd.ops import _p, _stream
 

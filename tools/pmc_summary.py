@@ -93,7 +93,12 @@ if pmc:
     print("wide", json.dumps(pmc, indent=1)[:800])
 json.dump(traffic, open(traffic_path, "w"), indent=1)
 # the XGB member (tools/bench_configs.py --only 7, PHASE=xgb): per-dispatch-size
-# kernel time from the trace, FETCH_SIZE per launch (x2, gfx950 rule above)
+# kernel time from the trace, FETCH_SIZE per launch (x2, gfx950 rule above).
+# Both predict kernels (k_xgb_lanes, k_xgb_walk), not the one-off table build.
+def is_xgb_predict(name):
+    return "k_xgb_" in name and "k_xgb_lane_table" not in name
+
+
 xdir = os.path.join(prof, "xgb")
 if os.path.isdir(xdir):
     rows = list(csv.reader(open(os.path.join(xdir, "run_kernel_stats.csv"))))
@@ -104,14 +109,14 @@ if os.path.isdir(xdir):
         w.writerows(body)
     by_grid = {}
     for r in csv.DictReader(open(os.path.join(xdir, "run_kernel_trace.csv"))):
-        if "k_xgb_walk" in r["Kernel_Name"]:
+        if is_xgb_predict(r["Kernel_Name"]):
             frames = int(r["Grid_Size_X"]) // int(r["Workgroup_Size_X"]) * 64
             by_grid.setdefault(frames, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-6)
     fetch = {}
     path = os.path.join(prof, "fetch_xgb", "run_counter_collection.csv")
     if os.path.exists(path):
         for r in csv.DictReader(open(path)):
-            if "k_xgb_walk" in r["Kernel_Name"]:
+            if is_xgb_predict(r["Kernel_Name"]):
                 frames = int(r["Grid_Size"]) // int(r["Workgroup_Size"]) * 64
                 fetch.setdefault(frames, []).append(float(r["Counter_Value"]) * 1024 * 2)
     summary = {str(k): {"dispatches": len(v), "mean_ms": statistics.mean(v), "min_ms": min(v),
