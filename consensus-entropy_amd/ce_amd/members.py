@@ -56,7 +56,7 @@ def _picks_batch(session, picks, song_labels, U, C, dev):
                           max_rows=max_rows)
 
 
-def _session_predict(session, X, U, D, C, out, skip_excluded):
+def _session_predict(session, X, U, D, C, out, skip_excluded, out_dtypes=(torch.float64,)):
     """What a member's predict_proba_session hands to the users form of its
     predict_proba: the session's frame geometry and bitmap, checked against the
     member (U models, D features, C classes) and X from host numbers alone --
@@ -72,7 +72,7 @@ def _session_predict(session, X, U, D, C, out, skip_excluded):
     if X.shape[0] < session._rows:
         raise ValueError(f"X has {X.shape[0]} rows, the session's frame geometry names {session._rows}")
     if out is not None:
-        ops.check_users_out(out, X.shape[0], C)
+        ops.check_users_out(out, X.shape[0], C, out_dtypes)
     return dict(item_offsets=items, frame_offsets=f_off, frame_perm=f_perm,
                 excl=session.excl if skip_excluded else None, out=out)
 
@@ -372,3 +372,102 @@ class DeviceSGDClassifier:
     def state(self):
         """Host copies: dict of coef [U, K, D], intercept [U, K], t [U], status [U]."""
         return {k: getattr(self, k).cpu().numpy().copy() for k in ("coef", "intercept", "t", "status")}
+
+
+class DeviceXGBClassifier:
+    """U XGBClassifier members on the device: the reference's 'classifier_xgb'
+    (deam_classifier.py:226-232), one forest per user.  ``base``: the shared
+    pretrained model (xgboost JSON or an XgbForest); ``models``: every user's
+    full model (None entries, or ``models=None`` with ``U``, mean the base
+    itself).  The refit stays on the host: after
+    ``mod.fit(X_batch, y, xgb_model=mod.get_booster())`` (amg_test.py:507) hand
+    the new forest over with ``set_model(u, XgbForest.from_booster(mod))``.  A
+    ``set_model`` compares and packs that one model on the host; the device
+    arrays (shared base trees once, every user's own trees after them) are put
+    together again once, on the next predict or evaluate, which must be outside
+    a capture.  ``device``: where the tables live; X and the EvalSet must be on
+    it.  Depth <= 5."""
+
+    def __init__(self, base, models=None, U=None, device=None):
+        from .xgb import StackedForests, XgbForest
+
+        self.dev = _device(device)
+        self.base = base if isinstance(base, XgbForest) else XgbForest.from_json(base)
+        if models is None:
+            models = [None] * (1 if U is None else int(U))
+        elif U is not None and int(U) != len(models):
+            raise ValueError(f"U={U} but {len(models)} model(s) given")
+        if len(models) < 1:
+            raise ValueError("DeviceXGBClassifier needs at least one model")
+        self.models = [self._forest(m) for m in models]
+        self.U, self.C, self.G = len(self.models), self.base.n_classes, self.base.n_groups
+        self.D = self.base.num_feature
+        self._stacked = StackedForests(self.base, self.models)  # refuses models that disagree with the base
+
+    def _forest(self, m):
+        from .xgb import XgbForest
+
+        return None if m is None else (m if isinstance(m, XgbForest) else XgbForest.from_json(m))
+
+    def stacked(self):
+        """The users' forests as one ``ce_amd.xgb.StackedForests``."""
+        return self._stacked
+
+    def set_model(self, u, model):
+        """User u's forest after a host refit (JSON, an XgbForest, or None for
+        the base): checked against the base, compared with it and packed here;
+        no other user's trees are touched.  Returns self."""
+        if not 0 <= int(u) < self.U:
+            raise ValueError(f"user {u} outside [0, {self.U})")
+        forest = self._forest(model)
+        self._stacked.set(int(u), forest)  # raises before anything changes
+        self.models[int(u)] = forest
+        return self
+
+    def _check_dev(self, t, what):
+        d = t.device
+        if d.type != self.dev.type or (self.dev.index is not None and d.index != self.dev.index):
+            raise ValueError(f"{what} is on {d}, this member's tables on {self.dev}")
+
+    def forest(self, u=0):
+        """User u's full forest (an XgbForest)."""
+        return self.base if self.models[u] is None else self.models[u]
+
+    def predict_proba(self, X, u=0, out=None, out_dtype=torch.float32):
+        """Model u's predict_proba over the frames X [F, D] (ops.xgb_predict_proba, the one-forest path)."""
+        return ops.xgb_predict_proba(X, self.forest(u), out=out, out_dtype=out_dtype)
+
+    def _check_D(self, D):
+        if self.D and D != self.D:
+            raise ValueError(f"X has {D} features, this member {self.D}")
+
+    def predict_proba_session(self, X, session, out=None, skip_excluded=True, out_dtype=torch.float32):
+        """The predict step of an epoch (amg_test.py:435) for every forest in
+        one launch (ops.xgb_predict_proba_users), as
+        DeviceGaussianNB.predict_proba_session: bit for bit
+        ``predict_proba(X, u)`` on every row user u owns.  X float32 or float64;
+        the result float32 (xgboost's own; a float32 frame-level member of
+        ``select(frames=[...])``) or float64 (its exact upcast)."""
+        if isinstance(X, torch.Tensor) and X.dim() == 2:
+            self._check_D(X.shape[1])
+            self._check_dev(X, "X")
+        kw = _session_predict(session, X, self.U, X.shape[1] if isinstance(X, torch.Tensor) and X.dim() == 2 else self.D,
+                              self.C, out, skip_excluded, (torch.float32, torch.float64))
+        return ops.xgb_predict_proba_users(X, self.stacked(), out_dtype=out_dtype, **kw)
+
+    def evaluate(self, evalset, report=False):
+        """The evaluate step of an epoch for every forest, as
+        DeviceGaussianNB.evaluate (ops.xgb_score_users, ops.f1_weighted_users):
+        returns (f1 [U], cm [U, C, C]), and prf [U, C, 4] with report=True."""
+        if isinstance(evalset, EvalSet):
+            self._check_D(evalset.D)
+            self._check_dev(evalset.X, "the EvalSet")
+        kw = _evalset_args(evalset, self.U, evalset.D if isinstance(evalset, EvalSet) else self.D)
+        cm, _, _ = ops.xgb_score_users(evalset.X, self.stacked(), **kw)
+        return _f1_of(cm, report)
+
+    def state(self):
+        """Host copies of the stacked arrays: dict of nodes, leaves, tree_ids, group_offsets, depth."""
+        s = self.stacked()
+        return {"nodes": s.nodes.copy(), "leaves": s.leaves.copy(), "tree_ids": s.tree_ids.copy(),
+                "group_offsets": s.group_offsets.copy(), "depth": s.depth}

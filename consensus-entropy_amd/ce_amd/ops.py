@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import CE_BF16, CE_F32, CE_F64, call
-from .xgb import LANE_TABLE_DEPTH, XgbForest
+from .xgb import LANE_TABLE_DEPTH, StackedForests, XgbForest
 
 _DT = {torch.float32: CE_F32, torch.float64: CE_F64, torch.bfloat16: CE_BF16}
 LAYOUTS = ("MNC", "NMC")
@@ -551,11 +551,13 @@ def sgd_predict_proba(X, coef, intercept, out=None):
     return out
 
 
-def check_users_out(out, F, C):
-    """``out`` of the users forms: a float64 [F, C] view with unit column stride and rows that do not overlap."""
-    if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.dim() != 2 or \
+def check_users_out(out, F, C, dtypes=(torch.float64,)):
+    """``out`` of the users forms: a float64 (or one of ``dtypes``) [F, C] view with unit column stride and rows
+    that do not overlap."""
+    if not isinstance(out, torch.Tensor) or out.dtype not in dtypes or out.dim() != 2 or \
             tuple(out.shape) != (F, C) or (C > 1 and out.stride(1) != 1) or (F > 1 and out.stride(0) < C):
-        raise ValueError(f"out must be a float64 [F={F}, C={C}] view with unit column stride")
+        names = "/".join(str(d).split(".")[1] for d in dtypes)
+        raise ValueError(f"out must be a {names} [F={F}, C={C}] view with unit column stride")
 
 
 def _users_geom(item_offsets, frame_offsets, frame_perm, excl):
@@ -573,16 +575,20 @@ def _users_geom(item_offsets, frame_offsets, frame_perm, excl):
     return U, item_offsets, frame_offsets, frame_perm
 
 
-def _users_args(X, C, item_offsets, frame_offsets, frame_perm, excl, out):
-    """The tail the users forms share: the geometry (_users_geom) and ``out``.
+def _users_args(X, C, item_offsets, frame_offsets, frame_perm, excl, out, out_dtype=torch.float64,
+                dtypes=(torch.float64,)):
+    """The tail the users forms share: the geometry (_users_geom) and ``out``
+    (a new one of ``out_dtype``; a given one of one of ``dtypes``).
     Returns (U, item_offsets, frame_offsets, frame_perm, out)."""
     F = X.shape[0]
     U, item_offsets, frame_offsets, frame_perm = _users_geom(item_offsets, frame_offsets, frame_perm, excl)
     if out is None:
         # rows of excluded songs are not written: a new tensor is zero there, the rule of frames_consensus
-        out = (torch.zeros if excl is not None else torch.empty)((F, C), dtype=torch.float64, device=X.device)
+        if out_dtype not in dtypes:
+            raise ValueError(f"out_dtype must be one of {dtypes}")
+        out = (torch.zeros if excl is not None else torch.empty)((F, C), dtype=out_dtype, device=X.device)
     _on_gpu(out, "out")
-    check_users_out(out, F, C)
+    check_users_out(out, F, C, dtypes)
     return U, item_offsets, frame_offsets, frame_perm, out
 
 
@@ -669,12 +675,12 @@ def _labels_i32(y, F):
 
 
 def _score_args(X, C, score_cols, U_models, item_offsets, frame_offsets, frame_perm, excl, y, return_pred,
-                return_scores):
-    """The tail the two score launches share.  Returns (U, item_offsets,
+                return_scores, scores_dtype=torch.float64):
+    """The tail the score launches share.  Returns (U, item_offsets,
     frame_offsets, frame_perm, y, cm, pred, scores): cm a new int64 [U, C, C]
     (the entry point zero-fills it), pred a new int32 [F] of -1 and scores a new
-    float64 [F, score_cols] of NaN where asked for -- what a row that is not
-    counted keeps."""
+    float64 (``scores_dtype``) [F, score_cols] of NaN where asked for -- what a
+    row that is not counted keeps."""
     F = X.shape[0]
     U, item_offsets, frame_offsets, frame_perm = _users_geom(item_offsets, frame_offsets, frame_perm, excl)
     if U != U_models:
@@ -682,7 +688,7 @@ def _score_args(X, C, score_cols, U_models, item_offsets, frame_offsets, frame_p
     y = _labels_i32(y, F)
     cm = torch.empty((U, C, C), dtype=torch.int64, device=X.device)
     pred = torch.full((F,), -1, dtype=torch.int32, device=X.device) if return_pred else None
-    scores = torch.full((F, score_cols), math.nan, dtype=torch.float64, device=X.device) if return_scores else None
+    scores = torch.full((F, score_cols), math.nan, dtype=scores_dtype, device=X.device) if return_scores else None
     return U, item_offsets, frame_offsets, frame_perm, y, cm, pred, scores
 
 
@@ -1036,6 +1042,62 @@ def xgb_predict_proba(X, forest, out=None, out_dtype=torch.float32):
         call("ce_xgb_predict_proba", _p(X), _DT[X.dtype], F, D, X.stride(0), _p(nodes), _p(leaves), _p(goff), G,
              depth, float(forest.base_margin), C, _p(out), _DT[out.dtype], out.stride(0), _stream(X.device))
     return out
+
+
+_XGB_DT = (torch.float32, torch.float64)
+
+
+def _xgb_users_model(X, stacked):
+    """The stacked forests of U users over the frames X.  Returns (F, D, the
+    entry points' forest arguments) -- the lane table is built for X's D on
+    first use (outside a capture) and cached."""
+    F, D = _check_X(X, _XGB_DT)
+    if not isinstance(stacked, StackedForests):
+        raise TypeError("stacked must be a ce_amd.xgb.StackedForests")
+    if stacked.max_feature >= D:
+        raise ValueError(f"the forests split on feature {stacked.max_feature} but X has {D} columns")
+    table, ids, goff = stacked.device(X.device, D)
+    return F, D, (_p(table), stacked.TT, _p(ids), stacked.L, _p(goff), stacked.G, stacked.depth,
+                  stacked.base_margin, stacked.C)
+
+
+def xgb_predict_proba_users(X, stacked, item_offsets, frame_offsets, frame_perm=None, excl=None, out=None,
+                            out_dtype=torch.float32):
+    """xgb_predict_proba for U forests at once (ce_xgb_predict_proba_users):
+    every frame row of X [F, D] f32/f64 is predicted by the forest of the user
+    who owns it, in one launch.  ``stacked``: a ``ce_amd.xgb.StackedForests``
+    (the shared base trees once, every user's own after them; depth <= 5).
+    Geometry, ``excl`` and ``out`` as gnb_predict_proba_users, with ``out``
+    float32 (what xgboost returns) or float64 (its exact upcast); per row the
+    bits are xgb_predict_proba's with that user's full model.  Nothing is
+    synchronised."""
+    F, D, forest = _xgb_users_model(X, stacked)
+    U, item_offsets, frame_offsets, frame_perm, out = _users_args(
+        X, stacked.C, item_offsets, frame_offsets, frame_perm, excl, out, out_dtype, _XGB_DT)
+    if U != stacked.U:
+        raise ValueError(f"item_offsets names {U} user(s), stacked holds {stacked.U} forest(s)")
+    call("ce_xgb_predict_proba_users", _p(X), _DT[X.dtype], F, D, X.stride(0), *forest, U, _p(item_offsets),
+         _p(frame_offsets), _p(frame_perm), _p(excl), _p(out), _DT[out.dtype], max(out.stride(0), stacked.C),
+         _stream(X.device))
+    return out
+
+
+def xgb_score_users(X, stacked, item_offsets, frame_offsets, y, frame_perm=None, excl=None, return_pred=False,
+                    return_proba=False):
+    """gnb_score_users for U XGBoost forests (ce_xgb_score_users;
+    amg_test.py:513): every owned row is labelled by XGBClassifier.predict's
+    rule on the float32 probabilities xgb_predict_proba_users forms
+    (xgboost/sklearn.py:981-985: np.argmax of the probabilities, or p > 0.5 for
+    a binary model) and counted in cm[u, y, pred].  Returns (cm int64 [U, C, C],
+    pred int32 [F] or None, proba f32 [F, C] or None); rows not counted keep -1
+    in pred and NaN in proba.  Nothing is synchronised."""
+    F, D, forest = _xgb_users_model(X, stacked)
+    U, item_offsets, frame_offsets, frame_perm, y, cm, pred, proba = _score_args(
+        X, stacked.C, stacked.C, stacked.U, item_offsets, frame_offsets, frame_perm, excl, y, return_pred,
+        return_proba, torch.float32)
+    call("ce_xgb_score_users", _p(X), _DT[X.dtype], F, D, X.stride(0), *forest, U, _p(item_offsets), _p(frame_offsets),
+         _p(frame_perm), _p(excl), _p(y), _p(cm), _p(pred), _p(proba), stacked.C, _stream(X.device))
+    return cm, pred, proba
 
 
 def _check_q(q):

@@ -139,11 +139,15 @@ class XgbForest:
         return d
 
     # ---- the device layout --------------------------------------------------
-    def pack(self):
+    def pack(self, depth=None):
         """(nodes u32 [T, 2^d - 1, 2], leaves f32 [T, 2^d], group_offsets i32 [G+1], depth):
-        perfect trees, group-major, model order inside a group."""
-        if self._packed is not None:
-            return self._packed
+        perfect trees, group-major, model order inside a group.  ``depth``: pad
+        to a common depth >= the forest's own (a deeper perfect tree repeats
+        the leaf below it, so the bits do not change); cached per depth."""
+        if self._packed is None:
+            self._packed = {}
+        if depth in self._packed:
+            return self._packed[depth]
         G = self.n_groups
         if G < 1 or G > MAX_GROUPS:
             raise ValueError(f"{G} groups: 1..{MAX_GROUPS} supported")
@@ -151,6 +155,10 @@ class XgbForest:
                 self.tree_info.min() < 0 or self.tree_info.max() >= G)):
             raise ValueError("tree_info does not match the trees / groups")
         d = self.depth()
+        if depth is not None:
+            if int(depth) < d:
+                raise ValueError(f"depth={depth} below the forest's own depth {d}")
+            d = int(depth)
         if d > MAX_DEPTH:
             raise ValueError(f"tree depth {d} > {MAX_DEPTH}")
         NI, NL = (1 << d) - 1, 1 << d
@@ -179,8 +187,10 @@ class XgbForest:
         counts = np.bincount(self.tree_info, minlength=G)
         goff = np.zeros(G + 1, dtype=np.int32)
         goff[1:] = np.cumsum(counts)
-        self._packed = (nodes, leaves, goff, d)
-        return self._packed
+        self._packed[depth] = (nodes, leaves, goff, d)
+        if depth is None:
+            self._packed.setdefault(d, self._packed[None])
+        return self._packed[depth]
 
     def max_feature(self):
         return max((int(tr["split"][tr["left"] != -1].max(initial=-1)) for tr in self.trees), default=-1)
@@ -215,6 +225,179 @@ class XgbForest:
             self._dev[key] = (torch.from_numpy(nodes.view(np.int32)).to(key),
                               torch.from_numpy(leaves).to(key), torch.from_numpy(goff).to(key), d)
         return self._dev[key]
+
+
+def _as_forest(model):
+    return model if isinstance(model, XgbForest) else XgbForest.from_json(model)
+
+
+def _same_tree(a, b):
+    return all(np.array_equal(a[k], b[k]) for k in ("left", "right", "split", "cond", "default_left"))
+
+
+def continued_model(model, more):
+    """What ``XGBClassifier.fit(X, y, xgb_model=booster)`` (amg_test.py:507)
+    does to the booster's JSON, given the rounds it grew as a model of their
+    own: a copy of ``model`` (a JSON dict) with ``more``'s trees appended, ids
+    and ``tree_info`` continued.  ``base_score`` and the objective stay
+    ``model``'s, as continued training keeps them."""
+    import copy
+
+    out = copy.deepcopy(model)
+    m, mm = out["learner"]["gradient_booster"]["model"], more["learner"]["gradient_booster"]["model"]
+    for k in ("objective", "learner_model_param"):
+        a, b = model["learner"][k], more["learner"][k]
+        if k == "objective":
+            a, b = a.get("name"), b.get("name")
+        else:
+            a, b = int(a.get("num_class", "0")), int(b.get("num_class", "0"))
+        if a != b:
+            raise ValueError(f"continued_model: the models disagree on {k} ({a!r} vs {b!r})")
+    for t in copy.deepcopy(mm["trees"]):
+        t["id"] = len(m["trees"])
+        m["trees"].append(t)
+    m["tree_info"] = list(m["tree_info"]) + list(mm["tree_info"])
+    m["gbtree_model_param"]["num_trees"] = str(len(m["trees"]))
+    return out
+
+
+def _check_against_base(base, f, u):
+    """Raise ValueError where model u cannot share launches with the base."""
+    for what in ("objective", "num_class", "num_feature"):
+        if getattr(f, what) != getattr(base, what):
+            raise ValueError(f"model {u} disagrees with the base on {what}: "
+                             f"{getattr(f, what)!r} vs {getattr(base, what)!r}")
+    if np.float32(f.base_score).view(np.uint32) != np.float32(base.base_score).view(np.uint32):
+        raise ValueError(f"model {u} disagrees with the base on base_score: {f.base_score!r} vs {base.base_score!r}")
+
+
+def _own_trees(base, f):
+    """(continues, own): whether f's first trees are the base's (node arrays and
+    tree_info), and the trees stored for it -- its tail then, else all of f --
+    as an XgbForest of their own, which keeps their packed arrays per depth."""
+    nb = len(base.trees)
+    cont = f is base or (len(f.trees) >= nb and np.array_equal(f.tree_info[:nb], base.tree_info) and
+                         all(_same_tree(f.trees[t], base.trees[t]) for t in range(nb)))
+    own = XgbForest(f.trees[nb:] if cont else f.trees, f.tree_info[nb:] if cont else f.tree_info,
+                    f.num_class, f.base_score, f.objective, f.num_feature)
+    return cont, own
+
+
+class StackedForests:
+    """Many users' forests over one set of packed trees (csrc/ce_xgb_users.hpp).
+    ``base``: the shared pretrained model; ``models[u]``: user u's FULL model
+    (JSON, an XgbForest, or None for the base itself).  Where a model's first
+    trees equal the base's (node arrays and tree_info) only its tail is stored;
+    otherwise the whole forest is stored as the user's own trees.  Raises
+    ValueError when a model disagrees with the base on the objective,
+    num_class, base_score or the feature range, or when the common depth is
+    above LANE_TABLE_DEPTH.
+
+    The arrays -- ``nodes`` u32 [TT, 2^d - 1, 2], ``leaves`` f32 [TT, 2^d],
+    ``tree_ids`` i32 [L], ``group_offsets`` i32 [U * G + 1], ``depth`` -- hold
+    the base's trees first (group-major, as ``base.pack``), then every user's
+    own; user u's group g owns tree_ids[group_offsets[u G + g] :
+    group_offsets[u G + g + 1]], in the order the reference adds them to
+    preds[g].  They are put together on first use and again after a ``set``:
+    a ``set`` compares and packs the one model it is given, every other user's
+    packed trees are kept, so the stacking itself is concatenation.
+    ``device(device, D)`` builds the lane table for X with D columns
+    (ce_xgb_lane_table) and caches it per (device, D) until the next ``set``."""
+
+    def __init__(self, base, models):
+        self.base = _as_forest(base)
+        if len(models) < 1:
+            raise ValueError("stack_forests needs at least one model")
+        self.U, self.G, self.C = len(models), self.base.n_groups, self.base.n_classes
+        self.base_margin = float(self.base.base_margin)
+        self._base_depth, self._base_feature = self.base.depth(), self.base.max_feature()
+        self._own = [self._entry(u, m) for u, m in enumerate(models)]
+        self._check_depth(self._own)
+        self._arrays, self._dev = None, {}
+
+    def _entry(self, u, model):
+        f = self.base if model is None else _as_forest(model)
+        _check_against_base(self.base, f, u)
+        cont, own = _own_trees(self.base, f)
+        return cont, own, own.depth(), own.max_feature()  # both walk every tree: once per model
+
+    def _check_depth(self, own):
+        depth = max([self._base_depth] + [e[2] for e in own])
+        if depth > LANE_TABLE_DEPTH:
+            raise ValueError(f"common tree depth {depth} > {LANE_TABLE_DEPTH}: the users form holds lane tables only")
+        return depth
+
+    def set(self, u, model):
+        """User u's full model from now on; raises before anything changes."""
+        entry = self._entry(u, model)
+        own = list(self._own)
+        own[u] = entry
+        self._check_depth(own)
+        self._own, self._arrays, self._dev = own, None, {}
+
+    def arrays(self):
+        """(nodes, leaves, tree_ids, group_offsets, depth)."""
+        if self._arrays is None:
+            depth, G = self._check_depth(self._own), self.G
+            bn, bl, bgoff, _ = self.base.pack(depth)
+            base_ids = [np.arange(bgoff[g], bgoff[g + 1], dtype=np.int64) for g in range(G)]
+            nodes, leaves, ids, goff = [bn], [bl], [], [0]
+            row0 = len(self.base.trees)
+            for cont, t, _, _ in self._own:
+                tn, tl, tgoff, _ = t.pack(depth)
+                nodes.append(tn)
+                leaves.append(tl)
+                for g in range(G):
+                    if cont:
+                        ids.append(base_ids[g])
+                    ids.append(row0 + np.arange(tgoff[g], tgoff[g + 1], dtype=np.int64))
+                    goff.append(goff[-1] + (len(base_ids[g]) if cont else 0) + int(tgoff[g + 1] - tgoff[g]))
+                row0 += len(t.trees)
+            if row0 >= 1 << 24 or goff[-1] >= 1 << 31:
+                raise ValueError(f"{row0} stored trees / {goff[-1]} logical trees: too many for the users form")
+            self._arrays = (np.concatenate(nodes), np.concatenate(leaves), np.concatenate(ids).astype(np.int32),
+                            np.asarray(goff, dtype=np.int32), depth)
+        return self._arrays
+
+    nodes = property(lambda self: self.arrays()[0])
+    leaves = property(lambda self: self.arrays()[1])
+    tree_ids = property(lambda self: self.arrays()[2])
+    group_offsets = property(lambda self: self.arrays()[3])
+    depth = property(lambda self: self.arrays()[4])
+    TT = property(lambda self: int(self.arrays()[0].shape[0]))
+    L = property(lambda self: int(self.arrays()[2].shape[0]))
+
+    @property
+    def max_feature(self):
+        """The highest feature a stored tree splits on (-1: none does)."""
+        return max([self._base_feature] + [e[3] for e in self._own])
+
+    def device(self, device, D):
+        """(table i32 [2, TT, 64, 2], tree_ids i32 [L], group_offsets i32 [U G + 1]) on ``device``."""
+        import torch
+
+        from . import _lib
+        from .ops import _p, _stream, call
+
+        key = (torch.device(device), int(D))
+        if key not in self._dev:
+            dev = key[0]
+            nodes, leaves, tree_ids, goff, depth = self.arrays()
+            TT = int(nodes.shape[0])
+            table = torch.zeros((2, max(TT, 1), 64, 2), dtype=torch.int32, device=dev)
+            if TT:
+                nd = torch.from_numpy(nodes.view(np.int32)).to(dev)
+                lv = torch.from_numpy(leaves).to(dev)
+                _lib.load()
+                call("ce_xgb_lane_table", _p(nd), _p(lv), TT, depth, int(D), _p(table), _stream(dev))
+            self._dev[key] = (table, torch.from_numpy(tree_ids).to(dev), torch.from_numpy(goff).to(dev))
+        return self._dev[key]
+
+
+def stack_forests(base, models):
+    """``StackedForests(base, models).arrays()``: (nodes, leaves, tree_ids,
+    group_offsets, depth) of many users' forests over one set of packed trees."""
+    return StackedForests(base, models).arrays()
 
 
 def synthetic_model(n_rounds=100, num_class=4, max_depth=5, num_feature=260, seed=1987, p_stop=0.15,

@@ -39,46 +39,6 @@ struct ScoreOut {
     int64_t lds;
 };
 
-// np.argmax over s[0 .. C): the first maximum; a NaN wins at its first occurrence
-template <int N>
-__device__ __forceinline__ int np_argmax(const double (&s)[N], int C) {
-    int best = 0;
-    double mp = s[0];
-    if (mp != mp) return 0;
-    for (int c = 1; c < C; ++c) {
-        if (!(s[c] <= mp)) {
-            mp = s[c];
-            best = c;
-            if (mp != mp) break;
-        }
-    }
-    return best;
-}
-
-// The block's counters of the run's user: flush() where the tables change hands
-// (every thread calls it behind a barrier that ends the previous run's bumps; a
-// barrier follows before the next run's), and last() after the walk.
-struct ScoreCounts {
-    int* lcm;  // [C * C] in LDS
-    unsigned long long* cm;
-    int CC, cur;
-    __device__ __forceinline__ void flush(int u) {
-        if ((int)threadIdx.x < CC) {
-            const int v = lcm[threadIdx.x];
-            if (cur >= 0 && v) atomicAdd(cm + (int64_t)cur * CC + threadIdx.x, (unsigned long long)v);
-            lcm[threadIdx.x] = 0;
-        }
-        cur = u;
-    }
-    __device__ __forceinline__ void last() {
-        __syncthreads();  // block-uniform: the walk's returns are
-        if (cur >= 0 && (int)threadIdx.x < CC) {
-            const int v = lcm[threadIdx.x];
-            if (v) atomicAdd(cm + (int64_t)cur * CC + threadIdx.x, (unsigned long long)v);
-        }
-    }
-};
-
 // One frame's outputs from the lanes of its 8-lane group: every lane holds the
 // same s[0 .. NS) and pred.  Lane 0 counts and writes pred, lane j < NS column j.
 template <int N>

@@ -72,11 +72,13 @@ __device__ __forceinline__ bool users_frame(const UsersGeom& ug, int64_t F, int6
 // (what can be issued before the tables change hands: the first loads),
 // stage(u) (user u's parameters into LDS; it owns its barriers, every thread
 // of the block calls it), then run(u, p, e) (the frames; no barrier inside).
-template <class Pre, class Stage, class Run>
+// ROUND: what a share is a multiple of (the linear members' pass of 4 waves x 8
+// frames; the XGBoost member's 64-frame tile, ce_xgb_users.hpp).
+template <int ROUND = 32, class Pre, class Stage, class Run>
 __device__ __forceinline__ void users_runs(const UsersGeom& ug, Pre&& pre, Stage&& stage, Run&& run) {
     const int64_t pb = users_first(ug, 0), pe = users_first(ug, ug.U);
     int64_t per = (pe - pb + gridDim.x - 1) / gridDim.x;
-    per = (per + 31) & ~(int64_t)31;
+    per = (per + ROUND - 1) & ~(int64_t)(ROUND - 1);
     int64_t p = pb + (int64_t)blockIdx.x * per;
     const int64_t p1 = p + per < pe ? p + per : pe;
     if (p >= p1) return;  // block-uniform
@@ -119,6 +121,47 @@ __device__ __forceinline__ void users_walk(const UsersGeom& ug, int64_t F, Stage
         }
     });
 }
+
+// ---- what the score finishes share (ce_members_score.hpp, ce_xgb_users.hpp) ----
+// np.argmax over s[0 .. C): the first maximum; a NaN wins at its first occurrence
+template <class T, int N>
+__device__ __forceinline__ int np_argmax(const T (&s)[N], int C) {
+    int best = 0;
+    T mp = s[0];
+    if (mp != mp) return 0;
+    for (int c = 1; c < C; ++c) {
+        if (!(s[c] <= mp)) {
+            mp = s[c];
+            best = c;
+            if (mp != mp) break;
+        }
+    }
+    return best;
+}
+
+// The block's counters of the run's user: flush() where the tables change hands
+// (every thread calls it behind a barrier that ends the previous run's bumps; a
+// barrier follows before the next run's), and last() after the walk.
+struct ScoreCounts {
+    int* lcm;  // [C * C] in LDS
+    unsigned long long* cm;
+    int CC, cur;
+    __device__ __forceinline__ void flush(int u) {
+        if ((int)threadIdx.x < CC) {
+            const int v = lcm[threadIdx.x];
+            if (cur >= 0 && v) atomicAdd(cm + (int64_t)cur * CC + threadIdx.x, (unsigned long long)v);
+            lcm[threadIdx.x] = 0;
+        }
+        cur = u;
+    }
+    __device__ __forceinline__ void last() {
+        __syncthreads();  // block-uniform: the walk's returns are
+        if (cur >= 0 && (int)threadIdx.x < CC) {
+            const int v = lcm[threadIdx.x];
+            if (v) atomicAdd(cm + (int64_t)cur * CC + threadIdx.x, (unsigned long long)v);
+        }
+    }
+};
 
 // ---- the kernels' bodies -------------------------------------------------------
 // A body is the walk with one family's staging and per-frame values; what is

@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "ce_abi.hpp"
+#include "ce_xgb_table.hpp"
 #include "ce_xgb_walk.hpp"
 
 using namespace ce;

@@ -1,0 +1,378 @@
+// ce_xgb_users.hpp -- the users form of the XGBoost member (SURVEY.md §8(f)5b /
+// 5c): after epoch 0 every user's forest is the shared pretrained trees plus
+// the rounds that user's own mod.fit(xgb_model=) appended (amg_test.py:507),
+// and every later predict_proba(X_train) (:435, :467) and predict(X_test)
+// (:513) has each frame row predicted by the forest of the user who owns it --
+// one launch for all users.
+//
+// Many forests over one lane table: `table` [2][TT][64] holds TT perfect trees
+// of one depth (ce_xgb_lane_table's format: the shared base trees once, then
+// every user's own), tree_ids [L] names a table row per logical tree, and
+// group_offsets [U * G + 1] is a CSR over tree_ids: user u's group g owns the
+// logical trees tree_ids[group_offsets[u G + g] .. group_offsets[u G + g + 1]),
+// in the order the reference adds them to preds[g].  So user u's forest is a
+// forest of ce_xgb_walk.hpp whose goff is group_offsets + u G, and the margin
+// chain (split_margins: the wave split, the ordered phases) is that header's
+// text over the layout UsersForest below.
+//
+// The geometry is the sessions' (UsersGeom, ce_members_users.hpp).  A block
+// takes a contiguous share of the CSR positions (a multiple of the 64-frame
+// tile), cuts it at the users' boundaries (users_runs) and walks one tile
+// after another: a tile is up to 64 consecutive positions of ONE user, so
+// every forest read of the walk is wave-uniform.  A position whose row is
+// outside [0, F) is neither read nor written, the rows of an excluded song are
+// never written, and a tile whose positions are all excluded or out of range
+// is skipped before its loads.  Every load of the staging is unconditional: an
+// inactive slot of a tile loads the row of the tile's first active slot (a
+// valid row, and no missing value the tile does not hold) and is never stored.
+//
+// Against the one-forest kernels: the staging (stage_tile, stage_tile_pairs),
+// LaneTableForest::walk8 and transform_store are restated here over the tile's
+// rows and tree_ids -- sharing their text changed the code of k_xgb_walk and
+// k_xgb_lanes -- and the tests hold the two to the same bits.
+#pragma once
+#include "ce_members_users.hpp"  // UsersGeom, users_runs, users_frame, ScoreCounts, np_argmax
+#include "ce_xgb_walk.hpp"
+
+namespace ce {
+
+// Lane-table walk over tree_ids: LaneTableForest's walk with logical tree k at
+// table row ids[k] (a wave-uniform scalar load; the debug build checks < TT).
+struct UsersForest : XgbGeom {
+    const uint2* table;     // [TT][64], fx with default_left in bit 31
+    const uint2* table_nd;  // [TT][64], fx without it
+    const int32_t* ids;     // [L]
+    int TT;
+
+    __device__ __forceinline__ int64_t row(int k) const {
+        CE_DASSERT(k >= 0 && k < goff_end);
+        const int t = ids[k];
+        CE_DASSERT(t >= 0 && t < TT);
+        return (int64_t)t * 64;
+    }
+    template <bool MISS, bool VALS>
+    __device__ __forceinline__ void walk8(const float* xs, int D, int t0, int t1, int lane, int (&li)[8],
+                                          float (&v)[8]) const {
+        (void)D;
+        const uint2* tb = MISS ? table : table_nd;
+        const uint2* tr[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) tr[j] = tb + row(tree(t0, j, t1));
+        uint2 e[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) e[j] = tr[j][lane];
+        const uint32_t lane4 = 4u * (uint32_t)lane;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            int h[4];  // the lane's heap index x 4: root 4, children 2 h + 4 b
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[j] = 4;
+            uint4 q0[4], q1[4];  // entries 0..3 of each tree: wave-uniform, scalar loads
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint4* p = reinterpret_cast<const uint4*>(tr[4 * g + j]);
+                q0[j] = p[0];
+                q1[j] = p[1];
+            }
+            if (depth >= 1) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) h[j] = table_right<MISS>(q0[j].z, q0[j].w, xs, lane4) ? 12 : 8;
+            }
+            if (depth >= 2) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool rt = h[j] == 12;
+                    const uint32_t f = rt ? q1[j].z : q1[j].x, th = rt ? q1[j].w : q1[j].y;
+                    h[j] = 2 * h[j] + (table_right<MISS>(f, th, xs, lane4) ? 4 : 0);
+                }
+            }
+            for (int lev = 2; lev < depth; ++lev) {
+                uint32_t f[4], th[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    f[j] = bperm(h[j], e[4 * g + j].x);
+                    th[j] = bperm(h[j], e[4 * g + j].y);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) h[j] = 2 * h[j] + (table_right<MISS>(f[j], th[j], xs, lane4) ? 4 : 0);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                li[4 * g + j] = (h[j] >> 2) - (NI + 1);
+                CE_DASSERT(li[4 * g + j] >= 0 && li[4 * g + j] <= NI);
+                if constexpr (VALS) v[4 * g + j] = __uint_as_float(bperm(h[j], e[4 * g + j].y));
+            }
+        }
+    }
+    __device__ __forceinline__ float value(int t, int li) const {
+        CE_DASSERT(li >= 0 && li <= NI);
+        return __uint_as_float(table[row(t) + NI + 1 + li].y);
+    }
+};
+
+struct XgbUsersForests {
+    const uint2* table;    // [2][TT][64]
+    const int32_t* ids;    // [L]
+    const int32_t* goff;   // [U * G + 1]
+    int TT, depth;
+    int64_t L;
+};
+
+// lane l's value of v, l wave-uniform
+__device__ __forceinline__ int64_t readlane64(int64_t v, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), l);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// stage_tile over the tile's rows: frame r of the tile is row rows[lane r] of X
+// (every lane of every wave holds the tile's 64 rows, one per lane).
+template <int XDT, int KF>
+__device__ __forceinline__ bool stage_rows(const void* X, int D, int64_t ld, int64_t rows, float* xs, int w, int lane) {
+    const int W = blockDim.x >> 6;
+    bool has_nan = false;
+    for (int r0 = w; r0 < kXgbTile; r0 += 2 * W) {  // wave-uniform
+        typename std::conditional<XDT == CE_F64, double, float>::type v[2][KF];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int r = min(r0 + h * W, kXgbTile - 1);
+            const int64_t row = readlane64(rows, r);
+#pragma unroll
+            for (int k = 0; k < KF; ++k) {
+                const int f = min(lane + 64 * k, D - 1);
+                if constexpr (XDT == CE_F64)
+                    v[h][k] = static_cast<const double*>(X)[row * ld + f];
+                else
+                    v[h][k] = static_cast<const float*>(X)[row * ld + f];
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int r = r0 + h * W;
+#pragma unroll
+            for (int k = 0; k < KF; ++k) {
+                const int f = lane + 64 * k;
+                if (f < D && r < kXgbTile) {
+                    const float x = (float)v[h][k];
+                    xs[f * kXgbCol + (r ^ lane)] = x;  // (f & 63) == lane
+                    has_nan |= __builtin_isnan(x);
+                }
+            }
+        }
+    }
+    return has_nan;
+}
+
+// stage_tile_pairs over the tile's rows (f64 frames, D >= 2)
+template <int KP>
+__device__ __forceinline__ bool stage_rows_pairs(const double* X, int D, int64_t ld, int64_t rows, float* xs, int w,
+                                                 int lane) {
+    const int W = blockDim.x >> 6;
+    bool has_nan = false;
+    for (int r0 = w; r0 < kXgbTile; r0 += 2 * W) {  // wave-uniform
+        double2 v[2][KP];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int r = min(r0 + h * W, kXgbTile - 1);
+            const int64_t row = readlane64(rows, r);
+#pragma unroll
+            for (int k = 0; k < KP; ++k) {
+                const int fl = min(2 * lane + 128 * k, D - 2);
+                const double* src = X + row * ld + fl;
+                v[h][k] = make_double2(src[0], src[1]);
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int r = r0 + h * W;
+#pragma unroll
+            for (int k = 0; k < KP; ++k) {
+                const int f = 2 * lane + 128 * k, fl = min(f, D - 2);
+                if (r < kXgbTile) {
+                    if (f < D) {  // f > fl only for f = D - 1 (odd D): the pair's second value
+                        const float x = (float)(f == fl ? v[h][k].x : v[h][k].y);
+                        xs[f * kXgbCol + (r ^ (f & 63))] = x;
+                        has_nan |= __builtin_isnan(x);
+                    }
+                    if (f + 1 < D && f == fl) {
+                        const float x = (float)v[h][k].y;
+                        xs[(f + 1) * kXgbCol + (r ^ ((f + 1) & 63))] = x;
+                        has_nan |= __builtin_isnan(x);
+                    }
+                }
+            }
+        }
+    }
+    return has_nan;
+}
+
+// transform_store's arithmetic: the float32 probabilities p[0 .. C) of the
+// tile's frame `lane` from its G margins mg[g * 64 + lane].
+__device__ __forceinline__ void users_proba(const float* mg, int G, int lane, float (&p)[kXgbMaxGroups]) {
+    if (G == 1) {  // binary:logistic -> [1 - p, p]
+        const float m = mg[lane];
+        const float p1 = 1.0f / (1.0f + glibc_expf(-m));
+        p[0] = 1.0f - p1;
+        p[1] = p1;
+    } else {  // multi:softprob -> common::Softmax
+        float mx = mg[lane];
+        for (int g = 1; g < G; ++g) mx = fmaxf(mg[g * 64 + lane], mx);
+        double wsum = 0.0;
+        for (int g = 0; g < G; ++g) {
+            p[g] = glibc_expf(mg[g * 64 + lane] - mx);
+            wsum += p[g];
+        }
+        const float ws = (float)wsum;
+        for (int g = 0; g < G; ++g) p[g] /= ws;
+    }
+}
+
+// dynamic LDS: the one-forest kernels' tile (xs, mg, the missing-value votes:
+// ce_xgb_lds_bytes), then the tile's rows [64] and the score finish's counters
+constexpr int kXgbUsersExtraLds = 64 * (int)sizeof(int64_t) + kXgbMaxGroups * kXgbMaxGroups * (int)sizeof(int);
+
+// The body: the users walk, one tile after another, with a finish `fin`:
+//   fin.restage(u)      the block moves to user u (every thread, behind a barrier)
+//   fin.row(p, C, row)  one frame's probabilities (wave 0, the lane of the frame)
+//   fin.done()          after the walk (every thread of the block)
+template <int XDT, int KF, class Fin>
+__device__ __forceinline__ void xgb_users(const XgbArgs& a, const XgbUsersForests& f, const UsersGeom& ug, Fin& fin) {
+    extern __shared__ float xsm[];
+    float* xs = xsm;                  // [D][kXgbCol] swizzled
+    float* mg = xsm + a.D * kXgbCol;  // [G][64] margins
+    uint32_t* nanw = reinterpret_cast<uint32_t*>(mg + a.G * 64);  // [16] the tile's missing-value votes
+    int64_t* rowl = reinterpret_cast<int64_t*>(nanw + 16);        // [64] the tile's rows (-1: not to be written)
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = w / a.S, s = w - g * a.S;
+    CE_DASSERT(f.depth <= kXgbLaneDepth);
+    auto stage = [&](int u) {
+        __syncthreads();  // the previous user's frames are counted
+        fin.restage(u);
+    };
+    auto run = [&](int u, int64_t p, int64_t e) {
+        const int64_t s0 = ug.item_offsets[u], s1 = ug.item_offsets[u + 1];
+        const int32_t* goff = f.goff + (int64_t)u * a.G;
+#ifdef CE_DEBUG
+        for (int k = 0; k < a.G; ++k) CE_DASSERT(goff[k] >= 0 && goff[k] <= goff[k + 1] && goff[k + 1] <= f.L);
+#endif
+        const UsersForest fl{XgbGeom{goff, f.depth, (1 << f.depth) - 1, (int)f.L}, f.table,
+                             f.table + (int64_t)f.TT * 64, f.ids, f.TT};
+        for (int64_t q0 = p; q0 < e; q0 += kXgbTile) {
+            // every wave works out the tile's 64 frames for itself (lane = frame): the same
+            // answer in every wave, so the skip is block-uniform and no barrier hands them on
+            // An optimisation barrier: the compiler may not hoist what it computes from the lane
+            // (the LDS addresses of the staging and the walk) out of the tile loop, where those
+            // values would stay in registers across every walk.  Chosen from the compiler's
+            // resource report alone, not timed: scratch per lane with / without it is 60 / 88 B
+            // for the reference's shape (f64, KF = 5), lower in 21 of the 24 instantiations and
+            // higher in the three f64 KF = 8 ones (profiles/xgb_users_codeobj.json).
+            int lane = threadIdx.x & 63;
+            asm volatile("" : "+v"(lane));
+            int64_t row = 0;
+            const bool act = users_frame(ug, a.F, s0, s1, q0 + lane, e, row);
+            const uint64_t m = __ballot(act);
+            if (m == 0) continue;  // nothing to load, walk or store
+            const int64_t rows = act ? row : readlane64(row, __builtin_ctzll(m));
+            // rowl, nanw and mg are free: every wave is past the previous tile's last phase barrier,
+            // wave 0 (the only reader after it) past its finish
+            if (w == 0) rowl[lane] = act ? row : -1;
+            bool has_nan;
+            if constexpr (XDT == CE_F64) {
+                if (a.D >= 2)
+                    has_nan = stage_rows_pairs<(KF + 1) / 2>(static_cast<const double*>(a.X), a.D, a.ld, rows, xs, w, lane);
+                else
+                    has_nan = stage_rows<XDT, KF>(a.X, a.D, a.ld, rows, xs, w, lane);
+            } else {
+                has_nan = stage_rows<XDT, KF>(a.X, a.D, a.ld, rows, xs, w, lane);
+            }
+            {
+                const bool wn = __ballot(has_nan) != 0;
+                if (lane == 0) nanw[w] = wn ? 1u : 0u;
+            }
+            __syncthreads();
+            bool any_nan = false;
+            for (int k = 0; k < (int)(blockDim.x >> 6); ++k) any_nan |= nanw[k] != 0u;
+            if (any_nan)
+                split_margins<UsersForest, true>(a, fl, xs, mg, g, s, lane);
+            else
+                split_margins<UsersForest, false>(a, fl, xs, mg, g, s, lane);
+            if (w == 0) {
+                const int64_t ro = rowl[lane];
+                if (ro >= 0) {
+                    float pr[kXgbMaxGroups];
+                    users_proba(mg, a.G, lane, pr);
+                    fin.row(pr, a.C, ro);
+                }
+            }
+        }
+    };
+    users_runs<kXgbTile>(ug, [](int, int64_t, int64_t) {}, stage, run);
+    fin.done();
+}
+
+// ---- the finishes ---------------------------------------------------------------
+template <int ODT>
+struct XgbProbaFin : NoCounts {
+    void* out;
+    int64_t ldo;
+    __device__ __forceinline__ void row(const float (&p)[kXgbMaxGroups], int C, int64_t ro) {
+        for (int c = 0; c < C; ++c) {
+            if constexpr (ODT == CE_F64)
+                static_cast<double*>(out)[ro * ldo + c] = (double)p[c];
+            else
+                static_cast<float*>(out)[ro * ldo + c] = p[c];
+        }
+    }
+};
+
+struct XgbScoreOut {
+    const int32_t* y;        // [F] by row of X
+    unsigned long long* cm;  // [U, C, C] counts (int64), zero before the launch
+    int32_t* pred;           // [F] by row of X, or nullptr
+    float* proba;            // [F, C] (row pitch ldp), or nullptr
+    int64_t ldp;
+};
+
+// XGBClassifier.predict's rule (xgboost/sklearn.py:981-985) on the float32
+// probabilities: np.argmax of the row (multi:softprob; not of the margins), or
+// p > 0.5 (binary:logistic; a NaN is class 0).
+struct XgbScoreFin {
+    XgbScoreOut o;
+    ScoreCounts cnt;
+    int G;
+    __device__ __forceinline__ void restage(int u) { cnt.flush(u); }
+    __device__ __forceinline__ void done() { cnt.last(); }
+    __device__ __forceinline__ void row(const float (&p)[kXgbMaxGroups], int C, int64_t ro) {
+        const int yv = o.y[ro];
+        if (yv < 0 || yv >= C) return;
+        const int pred = G == 1 ? (p[1] > 0.5f ? 1 : 0) : np_argmax(p, C);
+        atomicAdd(cnt.lcm + yv * C + pred, 1);
+        if (o.pred) o.pred[ro] = pred;
+        if (o.proba)
+            for (int c = 0; c < C; ++c) o.proba[ro * o.ldp + c] = p[c];
+    }
+};
+
+// KF as k_xgb_lanes: the row's 64-feature chunks the staging loads.  The forest
+// arrays are __restrict__ kernel arguments of their own: only so does the
+// compiler know that the finish's stores leave them alone and keep every
+// forest read of the later tiles a scalar load.
+template <int XDT, int ODT, int KF>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_xgb_users(
+    XgbArgs a, UsersGeom ug, const uint2* __restrict__ table, const int32_t* __restrict__ tree_ids,
+    const int32_t* __restrict__ group_offsets, int TT, int depth, int64_t L) {
+    XgbProbaFin<ODT> fin{{}, a.out, a.ldo};
+    xgb_users<XDT, KF>(a, XgbUsersForests{table, tree_ids, group_offsets, TT, depth, L}, ug, fin);
+}
+
+template <int XDT, int KF>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_xgb_score_users(
+    XgbArgs a, UsersGeom ug, XgbScoreOut o, const uint2* __restrict__ table, const int32_t* __restrict__ tree_ids,
+    const int32_t* __restrict__ group_offsets, int TT, int depth, int64_t L) {
+    extern __shared__ float xsm[];
+    int* lcm = reinterpret_cast<int*>(xsm + a.D * kXgbCol + a.G * 64 + 16 + 128);  // behind the tile's rows
+    XgbScoreFin fin{o, {lcm, o.cm, a.C * a.C, -1}, a.G};
+    xgb_users<XDT, KF>(a, XgbUsersForests{table, tree_ids, group_offsets, TT, depth, L}, ug, fin);
+}
+
+}  // namespace ce

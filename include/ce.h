@@ -444,6 +444,60 @@ size_t ce_xgb_lds_bytes(int32_t D, int32_t G);
 int ce_xgb_expf(const float *x, int64_t n, float *y, ce_stream_t stream);
 
 /*
+ * The users form of the XGBoost member (SURVEY.md §8(f)5b / 5c;
+ * csrc/ce_xgb_users.hpp, entries in csrc/ce_xgb_users.hip): after epoch 0 every
+ * user's forest is the shared pretrained trees plus the rounds that user's own
+ * mod.fit(xgb_model=) appended (amg_test.py:507; the refit stays on the host),
+ * and one launch has every frame row of X predicted by the forest of the user
+ * who owns it.  Depth <= 5 only (lane tables).
+ *   table         [2][TT][64][2] u32: TT perfect trees of one common `depth`,
+ *                 built by ce_xgb_lane_table for X with D columns -- the shared
+ *                 base trees once, then every user's own trees
+ *   tree_ids      [L] int32: the row of `table` of every logical tree
+ *   group_offsets [U * G + 1] int32, a CSR over tree_ids: user u's group g owns
+ *                 tree_ids[group_offsets[u G + g] .. group_offsets[u G + g + 1]),
+ *                 in the order the reference adds them to preds[g] (the base
+ *                 model's trees of group g in model order, then the user's
+ *                 appended ones); a group may own no tree (the base margin)
+ * base_margin, G, C, D and depth are common to all users.  The geometry
+ * (item_offsets [U + 1], frame_offsets, frame_perm_or_null, excl_or_null) is
+ * that of ce_gnb_predict_proba_users: a position whose row is outside [0, F)
+ * is neither read nor written, the rows of an excluded song are never written
+ * (a 64-frame tile without a row to write is skipped before its loads), a row
+ * no song owns is not touched.  out [F, C] out_dt F32 | F64 (the exact upcast),
+ * row stride ld_out.  Per row the bits are ce_xgb_predict_proba_lanes' with
+ * that user's forest.
+ * ce_xgb_score_users: the evaluate step (amg_test.py:513) -- the same float32
+ * probabilities, labelled by XGBClassifier.predict's rule
+ * (xgboost/sklearn.py:981-985: np.argmax of the PROBABILITIES for
+ * multi:softprob, the first maximum, a NaN at its first occurrence; p > 0.5 for
+ * binary:logistic) and counted in cm [U, C, C] int64 (zero-filled here by one
+ * stream-ordered memset), cm[u, y, pred]; y [F] by ROW of X, a label outside
+ * [0, C) is not counted and nothing is written for that row.  pred_or_null
+ * [F] int32 and proba_or_null [F, C] f32 (row stride ld_proba) by row of X.
+ * ce_f1_weighted_users turns cm into every user's weighted F1.
+ * CE_EINVAL: bad shapes, G / C other than G == C or (G == 1, C == 2), dtypes
+ * other than F32 / F64, a null pointer with F > 0, U < 1, L < 0;
+ * CE_EUNSUPPORTED: depth > 5.  F == 0 launches nothing (cm is zero-filled).
+ * Preconditions, checked in the debug build alone: ids in [0, TT), offsets
+ * non-decreasing and <= L, table built for this D.  One launch (and the
+ * memset), no workspace, nothing read back: capturable.  ce_last_kernel()
+ * names the kernel launched.
+ */
+int ce_xgb_predict_proba_users(const void *X, ce_dtype x_dt, int64_t F, int32_t D, int64_t ld,
+                               const uint32_t *table, int32_t TT, const int32_t *tree_ids, int64_t L,
+                               const int32_t *group_offsets, int32_t G, int32_t depth, float base_margin,
+                               int32_t C, int32_t U, const int64_t *item_offsets, const int64_t *frame_offsets,
+                               const int64_t *frame_perm_or_null, const uint32_t *excl_or_null, void *out,
+                               ce_dtype out_dt, int64_t ld_out, ce_stream_t stream);
+int ce_xgb_score_users(const void *X, ce_dtype x_dt, int64_t F, int32_t D, int64_t ld, const uint32_t *table,
+                       int32_t TT, const int32_t *tree_ids, int64_t L, const int32_t *group_offsets, int32_t G,
+                       int32_t depth, float base_margin, int32_t C, int32_t U, const int64_t *item_offsets,
+                       const int64_t *frame_offsets, const int64_t *frame_perm_or_null,
+                       const uint32_t *excl_or_null, const int32_t *y, int64_t *cm, int32_t *pred_or_null,
+                       float *proba_or_null, int64_t ld_proba, ce_stream_t stream);
+
+/*
  * glibc's f64 log as the engine evaluates it inside every entropy
  * (scipy.special.entr's log, amg_test.py:443; csrc/ce_glibc_log.hpp), exposed
  * for verification against the C library:
