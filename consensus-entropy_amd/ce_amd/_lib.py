@@ -60,6 +60,10 @@ SIGNATURES = {
                                           ctypes.c_float, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]),
     "ce_xgb_score_users": (_int, [_vp, _int, _i64, _i32, _i64, _vp, _i32, _vp, _i64, _vp, _i32, _i32, ctypes.c_float,
                                   _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ce_xgb_fit_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    "ce_xgb_fit_users": (_int, [_vp, _int, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _i32, _vp, _i64, _vp,
+                                _i32, _i32, ctypes.c_float, _i32, _i32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ce_xgb_lds_bytes": (_sz, [_i32, _i32]),
     "ce_xgb_expf": (_int, [_vp, _i64, _vp, _vp]),
     "ce_log_f64": (_int, [_vp, _i64, _vp, _vp]),

@@ -379,14 +379,19 @@ class DeviceXGBClassifier:
     (deam_classifier.py:226-232), one forest per user.  ``base``: the shared
     pretrained model (xgboost JSON or an XgbForest); ``models``: every user's
     full model (None entries, or ``models=None`` with ``U``, mean the base
-    itself).  The refit stays on the host: after
-    ``mod.fit(X_batch, y, xgb_model=mod.get_booster())`` (amg_test.py:507) hand
-    the new forest over with ``set_model(u, XgbForest.from_booster(mod))``.  A
-    ``set_model`` compares and packs that one model on the host; the device
-    arrays (shared base trees once, every user's own trees after them) are put
-    together again once, on the next predict or evaluate, which must be outside
-    a capture.  ``device``: where the tables live; X and the EvalSet must be on
-    it.  Depth <= 5."""
+    itself).  The refit runs on the device: ``fit`` / ``fit_picks`` grow the
+    rounds of ``mod.fit(X_batch, y, xgb_model=mod.get_booster())``
+    (amg_test.py:507) for every user in one launch and append them to the
+    stacked forests the predict and evaluate walks read; nothing of a tree
+    comes back to the host unless ``forest(u)``, ``models[u]`` or ``state()``
+    asks.  ``status`` (int32 [U], as on DeviceSGDClassifier) flags the users a
+    fit left alone.  A model trained elsewhere is still handed over with
+    ``set_model(u, ...)``, which compares and packs that one model on the host
+    and replaces that user's whole tail, device-grown trees included.  After a
+    ``fit`` or a ``set_model`` the device arrays are updated outside a capture:
+    neither call, nor the first predict or evaluate after a ``set_model``, is
+    graph-capturable.  ``device``: where the tables live; X and the EvalSet
+    must be on it.  Depth <= 5."""
 
     def __init__(self, base, models=None, U=None, device=None):
         from .xgb import StackedForests, XgbForest
@@ -399,10 +404,28 @@ class DeviceXGBClassifier:
             raise ValueError(f"U={U} but {len(models)} model(s) given")
         if len(models) < 1:
             raise ValueError("DeviceXGBClassifier needs at least one model")
-        self.models = [self._forest(m) for m in models]
-        self.U, self.C, self.G = len(self.models), self.base.n_classes, self.base.n_groups
+        self._models = [self._forest(m) for m in models]
+        self.U, self.C, self.G = len(self._models), self.base.n_classes, self.base.n_groups
         self.D = self.base.num_feature
-        self._stacked = StackedForests(self.base, self.models)  # refuses models that disagree with the base
+        self._stacked = StackedForests(self.base, self._models)  # refuses models that disagree with the base
+        self._status = None  # on the device from the first use on: the member is built without one
+
+    @property
+    def status(self):
+        """int32 [U] on the device, only ever set by ``fit``: 1 where a batch held a non-finite value, 2 where
+        it was not run."""
+        if self._status is None:
+            self._status = torch.zeros(self.U, dtype=torch.int32, device=self.dev)
+        return self._status
+
+    @property
+    def models(self):
+        """Every user's full model (None: the base itself) as a NEW list, read-only:
+        assigning into it changes nothing (``set_model`` is the way to hand a
+        model over), and after a ``fit`` it reads every grown tree of every user
+        back from the device.  ``forest(u)`` reads one user's."""
+        return [None if self._models[u] is None and not self._stacked.has_grown(u) else self.forest(u)
+                for u in range(self.U)]
 
     def _forest(self, m):
         from .xgb import XgbForest
@@ -421,7 +444,45 @@ class DeviceXGBClassifier:
             raise ValueError(f"user {u} outside [0, {self.U})")
         forest = self._forest(model)
         self._stacked.set(int(u), forest)  # raises before anything changes
-        self.models[int(u)] = forest
+        self._models[int(u)] = forest
+        return self
+
+    def fit(self, X, rows, labels, row_offsets=None, n_rounds=100, max_depth=5, **params):
+        """mod.fit(X[rows], labels, xgb_model=mod.get_booster()) for every
+        forest (amg_test.py:507), on the device: forest u grows ``n_rounds``
+        rounds of depth <= ``max_depth`` on rows[row_offsets[u]:row_offsets[u+1]]
+        (row_offsets=None: one forest, every row), given in X_train's order,
+        and the walks see them from the next call on (ops.xgb_fit_users, which
+        names the parameters it takes and those it refuses).  A forest with no
+        row is left untouched; one whose batch holds a non-finite value too,
+        with ``status[u]`` = 1.  If ``max_depth`` is above the stack's common
+        depth the stack is packed again at the new depth first.  Not
+        graph-capturable.  Returns self."""
+        if isinstance(X, torch.Tensor) and X.dim() == 2:
+            self._check_D(X.shape[1])
+            self._check_dev(X, "X")
+        ops.xgb_fit_users(X, rows, labels, self._stacked, row_offsets, n_rounds, max_depth, status=self.status, **params)
+        return self
+
+    def fit_picks(self, X, session, picks, song_labels, n_rounds=100, max_depth=5, **params):
+        """The retrain step of an epoch (amg_test.py:491-507) from a session's
+        picks, as DeviceGaussianNB.partial_fit_picks: the picks become songs,
+        the songs the frame rows of X_batch (ops.batch_rows), and every forest
+        grows its rounds on its own batch.  An epoch that picked nothing leaves
+        the forests as they are."""
+        rows, labels, row_offsets = _picks_batch(session, picks, song_labels, self.U, self.C, self.dev)
+        return self.fit(X, rows, labels, row_offsets, n_rounds, max_depth, **params)
+
+    def check_finite(self):
+        """Reads the flags (one device-to-host copy).  Raises a ValueError where
+        a fit met a non-finite value in a batch, a RuntimeError where a batch
+        was not run; the flags stay set."""
+        st = self.status.cpu().numpy()
+        if (st == 2).any():
+            raise RuntimeError(f"forest(s) {np.flatnonzero(st == 2).tolist()} were not fitted: too many rows")
+        if (st != 0).any():
+            raise ValueError(f"the batch of forest(s) {np.flatnonzero(st != 0).tolist()} holds a non-finite value, "
+                             "a row outside X or a label outside [0, C): they were left unchanged")
         return self
 
     def _check_dev(self, t, what):
@@ -430,8 +491,10 @@ class DeviceXGBClassifier:
             raise ValueError(f"{what} is on {d}, this member's tables on {self.dev}")
 
     def forest(self, u=0):
-        """User u's full forest (an XgbForest)."""
-        return self.base if self.models[u] is None else self.models[u]
+        """User u's full forest (an XgbForest); device-grown trees are read back."""
+        if not self._stacked.has_grown(u):
+            return self.base if self._models[u] is None else self._models[u]
+        return self._stacked.forest(u)
 
     def predict_proba(self, X, u=0, out=None, out_dtype=torch.float32):
         """Model u's predict_proba over the frames X [F, D] (ops.xgb_predict_proba, the one-forest path)."""

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import CE_BF16, CE_F32, CE_F64, call
-from .xgb import LANE_TABLE_DEPTH, StackedForests, XgbForest
+from .xgb import LANE_TABLE_DEPTH, MAX_FEATURES, StackedForests, XgbForest
 
 _DT = {torch.float32: CE_F32, torch.float64: CE_F64, torch.bfloat16: CE_BF16}
 LAYOUTS = ("MNC", "NMC")
@@ -1056,9 +1056,123 @@ def _xgb_users_model(X, stacked):
         raise TypeError("stacked must be a ce_amd.xgb.StackedForests")
     if stacked.max_feature >= D:
         raise ValueError(f"the forests split on feature {stacked.max_feature} but X has {D} columns")
-    table, ids, goff = stacked.device(X.device, D)
-    return F, D, (_p(table), stacked.TT, _p(ids), stacked.L, _p(goff), stacked.G, stacked.depth,
-                  stacked.base_margin, stacked.C)
+    table, cap, ids, L, goff, depth = stacked.device_args(X.device, D)
+    return F, D, (_p(table), cap, _p(ids), L, _p(goff), stacked.G, depth, stacked.base_margin, stacked.C)
+
+
+XGB_FIT_MAX_ROWS = 4096  # kXgbFitMaxRows: rows of one user's batch
+XGB_FIT_MAX_DEPTH = 5    # kXgbFitMaxDepth
+_XGB_FIT_NODES = 63
+
+
+def xgb_fit_users(X, rows, labels, stacked, row_offsets=None, n_rounds=100, max_depth=5, *, eta=0.3, reg_lambda=1.0,
+                  min_child_weight=1.0, gamma=0.0, alpha=0.0, objective="multi:softprob", sample_weight=None,
+                  status=None, return_margins=False):
+    """``XGBClassifier(max_depth).fit(X[rows], labels, xgb_model=booster)`` on
+    the device for U forests at once (ce_xgb_fit_users; amg_test.py:507):
+    ``n_rounds`` boosting rounds are grown on every user's batch on top of its
+    current forest and appended to ``stacked`` (a ``ce_amd.xgb.StackedForests``),
+    whose walks see them from the next call on.  X [F, D] f32/f64 frames (cast
+    to float32 like DMatrix; the batch must be dense and finite); user u's
+    batch is ``rows[row_offsets[u]:row_offsets[u+1]]`` of class ``labels[i]`` in
+    [0, C), in X_train's order (``batch_rows`` builds them); row_offsets=None
+    means one forest owning every row.  The arithmetic is the restatement of
+    tests/xgb_fit_ref.py, bit for bit (multi:softprob, exact grower, dense
+    columns); parity with xgboost 1.3.3 is unpinned.  Refused before any
+    launch: gamma or alpha other than 0, any objective but multi:softprob,
+    sample weights, max_depth above 5, D > 512, more than 4096 rows of one user.
+    ``status`` int32 [U] (zeroed when not given; only ever set): 1 where a
+    batch holds a non-finite value (that forest is left unchanged), 2 where it
+    was not run.  A user without rows gets no new tree.  Two small copies cross
+    the bus (row_offsets before the launch, the flags after it) and none of the
+    trees; the call synchronises and is not graph-capturable.  Returns a dict:
+    ``status``, ``active`` (host bool [U]: who got trees), ``trees`` (the
+    ``ce_amd.xgb.GrownTrees`` appended, its arrays on the device), ``margins``
+    (f32 [R, C], the batch's final margins, with return_margins)."""
+    from .xgb import GrownTrees
+
+    # what the fit does not take is refused first, from host values alone
+    if not isinstance(stacked, StackedForests):
+        raise TypeError("stacked must be a ce_amd.xgb.StackedForests")
+    if objective != "multi:softprob" or stacked.G < 2 or stacked.G != stacked.C:
+        raise ValueError(f"xgb_fit_users grows multi:softprob forests only (objective {objective!r}, "
+                         f"{stacked.G} group(s))")
+    if float(gamma) != 0.0 or float(alpha) != 0.0:
+        raise ValueError(f"gamma and alpha must be 0 (no pruning, no L1 term), got gamma={gamma} alpha={alpha}")
+    if sample_weight is not None:
+        raise ValueError("sample weights are not supported")
+    n_rounds, max_depth = int(n_rounds), int(max_depth)
+    if n_rounds < 1:
+        raise ValueError(f"n_rounds must be at least 1, got {n_rounds}")
+    if not 1 <= max_depth <= XGB_FIT_MAX_DEPTH:
+        raise ValueError(f"max_depth must lie in [1, {XGB_FIT_MAX_DEPTH}], got {max_depth}")
+    for name, v, lo in (("eta", eta, None), ("reg_lambda", reg_lambda, 0.0), ("min_child_weight", min_child_weight, 0.0)):
+        v = float(v)
+        if not math.isfinite(v) or (lo is None and v <= 0.0) or (lo is not None and v < lo):
+            raise ValueError(f"{name} out of range: {v}")
+    F, D = _check_X(X, _XGB_DT)
+    if D > MAX_FEATURES:
+        raise ValueError(f"X has {D} features: at most {MAX_FEATURES}")
+    if stacked.max_feature >= D:
+        raise ValueError(f"the forests split on feature {stacked.max_feature} but X has {D} columns")
+    U, C = stacked.U, stacked.C
+    rows = _i64(rows, "rows").reshape(-1)
+    _on_gpu(labels, "labels")
+    labels = labels.reshape(-1).to(torch.int32).contiguous()
+    if labels.numel() != rows.numel():
+        raise ValueError(f"labels must hold one class per row ({rows.numel()}), got {labels.numel()}")
+    if row_offsets is None:
+        if U != 1:
+            raise ValueError(f"{U} forests need row_offsets [U + 1]")
+        ro_host = np.array([0, rows.numel()], dtype=np.int64)
+        row_offsets = torch.from_numpy(ro_host).to(X.device)
+    else:
+        row_offsets = _i64(row_offsets, "row_offsets").reshape(-1)
+        if row_offsets.numel() != U + 1:
+            raise ValueError(f"row_offsets must hold U + 1 = {U + 1} entries")
+        ro_host = row_offsets.cpu().numpy()
+    counts = np.diff(ro_host)
+    if ro_host[0] != 0 or (counts < 0).any() or ro_host[-1] > rows.numel():
+        raise ValueError("row_offsets must start at 0, ascend and end within rows")
+    R, n_max = int(ro_host[-1]), int(counts.max(initial=0))
+    if n_max > XGB_FIT_MAX_ROWS:
+        raise ValueError(f"a user's batch holds {n_max} rows: at most {XGB_FIT_MAX_ROWS}")
+    if status is None:
+        status = torch.zeros(U, dtype=torch.int32, device=X.device)
+    _on_gpu(status, "status")
+    if status.dtype != torch.int32 or not status.is_contiguous() or status.numel() != U:
+        raise ValueError(f"status must be a contiguous int32 tensor of {U} flags")
+    out = {"status": status, "active": np.zeros(U, dtype=bool), "trees": None, "margins": None}
+    if R == 0:  # every batch is empty (an epoch that picked nothing): every forest stays as it is
+        return out
+    stacked.ensure_depth(max_depth)  # a deeper fit: the stack is packed again at the new depth, once
+    table, cap, ids, L, goff, depth = stacked.device_args(X.device, D)
+    dev, T = X.device, U * n_rounds * C
+    NI, NL = max((1 << depth) - 1, 1), 1 << depth
+    t = {"nodes": torch.zeros((T, NI, 2), dtype=torch.int32, device=dev),
+         "leaves": torch.zeros((T, NL), dtype=torch.float32, device=dev),
+         "left": torch.full((T, _XGB_FIT_NODES), -1, dtype=torch.int32, device=dev),
+         "right": torch.full((T, _XGB_FIT_NODES), -1, dtype=torch.int32, device=dev),
+         "split": torch.zeros((T, _XGB_FIT_NODES), dtype=torch.int32, device=dev),
+         "cond": torch.zeros((T, _XGB_FIT_NODES), dtype=torch.float32, device=dev),
+         "default_left": torch.zeros((T, _XGB_FIT_NODES), dtype=torch.uint8, device=dev),
+         "num_nodes": torch.zeros(T, dtype=torch.int32, device=dev)}
+    margins = torch.zeros((R, C), dtype=torch.float32, device=dev) if return_margins else None
+    flags = torch.zeros(U, dtype=torch.int32, device=dev)
+    ws_bytes = int(_lib.load().ce_xgb_fit_workspace_bytes(R, n_max, D, C, n_rounds))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    call("ce_xgb_fit_users", _p(X), _DT[X.dtype], F, D, X.stride(0), _p(rows), _p(labels), _p(row_offsets), U, R, n_max,
+         _p(table), cap, _p(ids), L, _p(goff), C, depth, float(stacked.base_margin), n_rounds, max_depth, float(eta),
+         float(reg_lambda), float(min_child_weight), _p(t["nodes"]), _p(t["leaves"]), _p(t["left"]), _p(t["right"]),
+         _p(t["split"]), _p(t["cond"]), _p(t["default_left"]), _p(t["num_nodes"]), _p(margins), _p(flags), _p(ws),
+         ws_bytes, _stream(dev))
+    fl = flags.cpu().numpy()  # the one read-back after the launch: who got trees
+    status.copy_(torch.maximum(status, flags))
+    out["active"] = (counts > 0) & (fl == 0)
+    out["trees"] = GrownTrees(t, U, n_rounds, C, depth, out["active"])
+    out["margins"] = margins
+    stacked.grow(out["trees"], dev, D, D - 1)
+    return out
 
 
 def xgb_predict_proba_users(X, stacked, item_offsets, frame_offsets, frame_perm=None, excl=None, out=None,

@@ -283,6 +283,58 @@ def _own_trees(base, f):
     return cont, own
 
 
+class GrownTrees:
+    """The trees one ``ops.xgb_fit_users`` call grew, on the device: slot
+    (u * rounds + r) * G + k holds round r, group k of user u, in the packed
+    form (``nodes``, ``leaves`` at ``depth``) and as the model's own node arrays
+    (``left``, ``right``, ``split``, ``cond``, ``default_left`` [T, 63],
+    ``num_nodes`` [T]).  ``active[u]``: user u's slots hold trees that are part
+    of its forest (it had rows, was not flagged, and no ``set`` replaced them).
+    ``host()`` copies the node arrays to the host, once, when someone asks.
+    Both forms stay on the device for as long as the stack refers to the call
+    (the packed form rebuilds lane tables after a ``set`` or for another D, the
+    node arrays are the model): about 1.45 KB per slot, slots of users without
+    new trees included -- 290 MB for 500 users x 100 rounds x 4 groups."""
+
+    NAMES = ("left", "right", "split", "cond", "default_left", "num_nodes")
+
+    def __init__(self, out, U, rounds, G, depth, active):
+        self.out, self.U, self.rounds, self.G, self.depth = out, int(U), int(rounds), int(G), int(depth)
+        self.active = np.array(active, dtype=bool)
+        self.T = self.U * self.rounds * self.G
+        self._host = self._packed = None
+
+    def host(self):
+        if self._host is None:
+            self._host = {k: self.out[k].cpu().numpy() for k in self.NAMES}
+        return self._host
+
+    def packed(self):
+        """(nodes u32 [T, NI, 2], leaves f32 [T, NL]) read back."""
+        if self._packed is None:
+            self._packed = (self.out["nodes"].cpu().numpy().view(np.uint32), self.out["leaves"].cpu().numpy())
+        return self._packed
+
+    def trees(self, u):
+        """User u's trees of this call in model order (round-major, group inside the round), and their groups."""
+        if not self.active[u]:
+            return [], []
+        h, trees, info = self.host(), [], []
+        for r in range(self.rounds):
+            for k in range(self.G):
+                t = (u * self.rounds + r) * self.G + k
+                n = int(h["num_nodes"][t])
+                trees.append({"left": h["left"][t, :n].copy(), "right": h["right"][t, :n].copy(),
+                              "split": h["split"][t, :n].copy(), "cond": h["cond"][t, :n].copy(),
+                              "default_left": h["default_left"][t, :n].copy()})
+                info.append(k)
+        return trees, info
+
+    def ids(self, u, g, row0):
+        """The table rows of user u's trees of group g, in round order."""
+        return row0 + (u * self.rounds + np.arange(self.rounds, dtype=np.int64)) * self.G + g
+
+
 class StackedForests:
     """Many users' forests over one set of packed trees (csrc/ce_xgb_users.hpp).
     ``base``: the shared pretrained model; ``models[u]``: user u's FULL model
@@ -296,13 +348,26 @@ class StackedForests:
     The arrays -- ``nodes`` u32 [TT, 2^d - 1, 2], ``leaves`` f32 [TT, 2^d],
     ``tree_ids`` i32 [L], ``group_offsets`` i32 [U * G + 1], ``depth`` -- hold
     the base's trees first (group-major, as ``base.pack``), then every user's
-    own; user u's group g owns tree_ids[group_offsets[u G + g] :
-    group_offsets[u G + g + 1]], in the order the reference adds them to
-    preds[g].  They are put together on first use and again after a ``set``:
-    a ``set`` compares and packs the one model it is given, every other user's
-    packed trees are kept, so the stacking itself is concatenation.
-    ``device(device, D)`` builds the lane table for X with D columns
-    (ce_xgb_lane_table) and caches it per (device, D) until the next ``set``."""
+    own, then the trees grown on the device (``grow``: one GrownTrees per fit
+    call, in call order); user u's group g owns tree_ids[group_offsets[u G + g]
+    : group_offsets[u G + g + 1]], in the order the reference adds them to
+    preds[g].  The host-packed part is put together on first use and again
+    after a ``set``: a ``set`` compares and packs the one model it is given,
+    every other user's packed trees are kept, so the stacking itself is
+    concatenation.  ``device(device, D)`` builds the lane table for X with D
+    columns (ce_xgb_lane_table) and caches it per (device, D) until the next
+    ``set``.
+
+    Device-grown tails: ``grow`` writes the new trees' lane tables straight
+    after the existing ones -- the table is kept with spare capacity and grown
+    geometrically when full -- and rebuilds ``tree_ids`` / ``group_offsets`` on
+    the host from per-user tree counts (index arithmetic; no tree content
+    crosses the bus).  ``forest(u)`` and the host arrays read the grown trees
+    back only when asked.  ``set(u, ...)`` replaces user u's whole tail, grown
+    trees included.  Memory grows with every fit: the lane table by 1 KB
+    per new tree (and it doubles when full), and the call's GrownTrees stays
+    on the device (1.45 KB per tree slot) until a ``set`` of every user it
+    served, or a change of the common depth, releases it."""
 
     def __init__(self, base, models):
         self.base = _as_forest(base)
@@ -311,9 +376,10 @@ class StackedForests:
         self.U, self.G, self.C = len(models), self.base.n_groups, self.base.n_classes
         self.base_margin = float(self.base.base_margin)
         self._base_depth, self._base_feature = self.base.depth(), self.base.max_feature()
+        self._min_depth, self._chunks, self._grown_feature, self._merged = 0, [], -1, set()
         self._own = [self._entry(u, m) for u, m in enumerate(models)]
         self._check_depth(self._own)
-        self._arrays, self._dev = None, {}
+        self._host, self._arrays, self._dev = None, None, {}
 
     def _entry(self, u, model):
         f = self.base if model is None else _as_forest(model)
@@ -322,76 +388,234 @@ class StackedForests:
         return cont, own, own.depth(), own.max_feature()  # both walk every tree: once per model
 
     def _check_depth(self, own):
-        depth = max([self._base_depth] + [e[2] for e in own])
+        depth = max([self._base_depth, self._min_depth] + [e[2] for e in own])
         if depth > LANE_TABLE_DEPTH:
             raise ValueError(f"common tree depth {depth} > {LANE_TABLE_DEPTH}: the users form holds lane tables only")
         return depth
+
+    def _materialise(self):
+        """Every device-grown tree becomes a host tree of its user's own forest
+        (one read-back): what a change of the common depth needs, since the
+        grown trees are packed at the depth of their fit."""
+        if not self._chunks:
+            return
+        own = list(self._own)
+        for u in range(self.U):
+            trees, info = self.grown_trees(u)
+            if trees:
+                cont, t, _, _ = own[u]
+                f = XgbForest(list(t.trees) + trees, list(t.tree_info) + info, t.num_class, t.base_score, t.objective,
+                              t.num_feature)
+                own[u] = (cont, f, f.depth(), f.max_feature())
+                self._merged.add(u)
+        self._own, self._chunks, self._grown_feature = own, [], -1
+        self._host, self._arrays, self._dev = None, None, {}
 
     def set(self, u, model):
         """User u's full model from now on; raises before anything changes."""
         entry = self._entry(u, model)
         own = list(self._own)
         own[u] = entry
-        self._check_depth(own)
-        self._own, self._arrays, self._dev = own, None, {}
+        depth = self._check_depth(own)
+        if self._chunks and depth != self._check_depth(self._own):
+            self._materialise()
+            own = list(self._own)
+            own[u] = entry
+        self._merged.discard(u)
+        for c in self._chunks:
+            c.active[u] = False
+        self._chunks = [c for c in self._chunks if c.active.any()]
+        self._own, self._host, self._arrays, self._dev = own, None, None, {}
 
-    def arrays(self):
-        """(nodes, leaves, tree_ids, group_offsets, depth)."""
-        if self._arrays is None:
-            depth, G = self._check_depth(self._own), self.G
+    def ensure_depth(self, depth):
+        """The common depth from now on is at least ``depth`` (a fit of deeper
+        trees): the stack is packed again at the new depth on next use."""
+        depth = int(depth)
+        if depth > LANE_TABLE_DEPTH:
+            raise ValueError(f"depth {depth} > {LANE_TABLE_DEPTH}: the users form holds lane tables only")
+        if depth > self._check_depth(self._own):
+            self._materialise()
+            self._min_depth = depth
+            self._host, self._arrays, self._dev = None, None, {}
+
+    def grown_trees(self, u):
+        """User u's device-grown trees in model order and their groups (read back)."""
+        trees, info = [], []
+        for c in self._chunks:
+            t, i = c.trees(u)
+            trees += t
+            info += i
+        return trees, info
+
+    def n_grown(self, u):
+        """How many device-grown trees user u's forest holds (a host number)."""
+        return sum(c.rounds * c.G for c in self._chunks if c.active[u])
+
+    def has_grown(self, u):
+        """Whether user u's forest holds trees grown on the device (still there, or since merged into its own)."""
+        return u in self._merged or self.n_grown(u) > 0
+
+    def forest(self, u):
+        """User u's full forest, device-grown trees included: a true XgbForest."""
+        cont, own, _, _ = self._own[u]
+        trees, info = self.grown_trees(u)
+        if cont and not own.trees and not trees:
+            return self.base
+        head, hinfo = (list(self.base.trees), list(self.base.tree_info)) if cont else ([], [])
+        return XgbForest(head + list(own.trees) + trees, hinfo + list(own.tree_info) + info, self.base.num_class,
+                         self.base.base_score, self.base.objective, self.base.num_feature)
+
+    def _host_rows(self):
+        """(nodes, leaves, [(cont, row0, tgoff) per user], depth, the base's group offsets): the host-packed
+        rows, put together once until the next ``set``."""
+        if self._host is None:
+            depth = self._check_depth(self._own)
             bn, bl, bgoff, _ = self.base.pack(depth)
-            base_ids = [np.arange(bgoff[g], bgoff[g + 1], dtype=np.int64) for g in range(G)]
-            nodes, leaves, ids, goff = [bn], [bl], [], [0]
+            nodes, leaves, users = [bn], [bl], []
             row0 = len(self.base.trees)
             for cont, t, _, _ in self._own:
                 tn, tl, tgoff, _ = t.pack(depth)
                 nodes.append(tn)
                 leaves.append(tl)
-                for g in range(G):
-                    if cont:
-                        ids.append(base_ids[g])
-                    ids.append(row0 + np.arange(tgoff[g], tgoff[g + 1], dtype=np.int64))
-                    goff.append(goff[-1] + (len(base_ids[g]) if cont else 0) + int(tgoff[g + 1] - tgoff[g]))
+                users.append((cont, row0, tgoff))
                 row0 += len(t.trees)
-            if row0 >= 1 << 24 or goff[-1] >= 1 << 31:
-                raise ValueError(f"{row0} stored trees / {goff[-1]} logical trees: too many for the users form")
-            self._arrays = (np.concatenate(nodes), np.concatenate(leaves), np.concatenate(ids).astype(np.int32),
-                            np.asarray(goff, dtype=np.int32), depth)
+            self._host = (np.concatenate(nodes), np.concatenate(leaves), users, depth, bgoff)
+        return self._host
+
+    def _logical(self):
+        """(tree_ids i32 [L], group_offsets i32 [U G + 1]): index arithmetic over per-user tree counts."""
+        _, _, users, _, bgoff = self._host_rows()
+        G = self.G
+        base_ids = [np.arange(bgoff[g], bgoff[g + 1], dtype=np.int64) for g in range(G)]
+        bases, row0 = [], users[-1][1] + len(self._own[-1][1].trees)
+        for c in self._chunks:
+            bases.append(row0)
+            row0 += c.T
+        ids, goff = [], [0]
+        for u, (cont, urow0, tgoff) in enumerate(users):
+            for g in range(G):
+                n = 0
+                if cont:
+                    ids.append(base_ids[g])
+                    n += len(base_ids[g])
+                ids.append(urow0 + np.arange(tgoff[g], tgoff[g + 1], dtype=np.int64))
+                n += int(tgoff[g + 1] - tgoff[g])
+                for c, b in zip(self._chunks, bases):
+                    if c.active[u]:
+                        ids.append(c.ids(u, g, b))
+                        n += c.rounds
+                goff.append(goff[-1] + n)
+        if row0 >= 1 << 24 or goff[-1] >= 1 << 31:
+            raise ValueError(f"{row0} stored trees / {goff[-1]} logical trees: too many for the users form")
+        return np.concatenate(ids).astype(np.int32), np.asarray(goff, dtype=np.int32), row0
+
+    def arrays(self):
+        """(nodes, leaves, tree_ids, group_offsets, depth); device-grown trees are read back."""
+        if self._arrays is None:
+            nodes, leaves, _, depth, _ = self._host_rows()
+            ids, goff, _ = self._logical()
+            if self._chunks:
+                packed = [c.packed() for c in self._chunks]
+                nodes = np.concatenate([nodes] + [p[0] for p in packed])
+                leaves = np.concatenate([leaves] + [p[1] for p in packed])
+            self._arrays = (nodes, leaves, ids, goff, depth)
         return self._arrays
 
     nodes = property(lambda self: self.arrays()[0])
     leaves = property(lambda self: self.arrays()[1])
     tree_ids = property(lambda self: self.arrays()[2])
     group_offsets = property(lambda self: self.arrays()[3])
-    depth = property(lambda self: self.arrays()[4])
-    TT = property(lambda self: int(self.arrays()[0].shape[0]))
-    L = property(lambda self: int(self.arrays()[2].shape[0]))
+    depth = property(lambda self: self._host_rows()[3])
+    TT = property(lambda self: int(self._host_rows()[0].shape[0]) + sum(c.T for c in self._chunks))
+    L = property(lambda self: int(self._logical()[0].shape[0]))
 
     @property
     def max_feature(self):
         """The highest feature a stored tree splits on (-1: none does)."""
-        return max([self._base_feature] + [e[3] for e in self._own])
+        return max([self._base_feature, self._grown_feature] + [e[3] for e in self._own])
 
-    def device(self, device, D):
-        """(table i32 [2, TT, 64, 2], tree_ids i32 [L], group_offsets i32 [U G + 1]) on ``device``."""
+    def _lane_rows(self, nodes, leaves, T, depth, D, dev):
+        """[2, T, 64, 2] lane tables of T packed trees on the device."""
         import torch
 
         from . import _lib
         from .ops import _p, _stream, call
 
+        table = torch.zeros((2, max(T, 1), 64, 2), dtype=torch.int32, device=dev)
+        if T:
+            _lib.load()
+            call("ce_xgb_lane_table", _p(nodes), _p(leaves), T, depth, int(D), _p(table), _stream(dev))
+        return table
+
+    def _device_state(self, device, D):
+        import torch
+
         key = (torch.device(device), int(D))
         if key not in self._dev:
             dev = key[0]
-            nodes, leaves, tree_ids, goff, depth = self.arrays()
-            TT = int(nodes.shape[0])
-            table = torch.zeros((2, max(TT, 1), 64, 2), dtype=torch.int32, device=dev)
-            if TT:
-                nd = torch.from_numpy(nodes.view(np.int32)).to(dev)
-                lv = torch.from_numpy(leaves).to(dev)
-                _lib.load()
-                call("ce_xgb_lane_table", _p(nd), _p(lv), TT, depth, int(D), _p(table), _stream(dev))
-            self._dev[key] = (table, torch.from_numpy(tree_ids).to(dev), torch.from_numpy(goff).to(dev))
+            nodes, leaves, _, depth, _ = self._host_rows()
+            ids, goff, TT = self._logical()
+            T0 = int(nodes.shape[0])
+            table = self._lane_rows(torch.from_numpy(nodes.view(np.int32)).to(dev), torch.from_numpy(leaves).to(dev), T0,
+                                    depth, D, dev)
+            if self._chunks:  # the grown trees' tables behind the host-packed ones, from their device arrays
+                full = torch.zeros((2, TT, 64, 2), dtype=torch.int32, device=dev)
+                full[:, :T0] = table[:, :T0]
+                row0 = T0
+                for c in self._chunks:
+                    full[:, row0:row0 + c.T] = self._lane_rows(c.out["nodes"].to(dev), c.out["leaves"].to(dev), c.T,
+                                                               depth, D, dev)
+                    row0 += c.T
+                table = full
+            self._dev[key] = {"table": table, "used": TT, "ids": torch.from_numpy(ids).to(dev),
+                              "goff": torch.from_numpy(goff).to(dev), "L": int(ids.shape[0])}
         return self._dev[key]
+
+    def device(self, device, D):
+        """(table i32 [2, capacity, 64, 2], tree_ids i32 [L], group_offsets i32 [U G + 1]) on ``device``."""
+        s = self._device_state(device, D)
+        return s["table"], s["ids"], s["goff"]
+
+    def device_args(self, device, D):
+        """(table, its capacity in trees, tree_ids, L, group_offsets, depth): what the
+        users entry points take, from host numbers alone (nothing is read back)."""
+        s = self._device_state(device, D)
+        return s["table"], int(s["table"].shape[1]), s["ids"], s["L"], s["goff"], self.depth
+
+    def attach(self, chunk, max_feature):
+        """The host half of ``grow``: the chunk's trees join their users' forests
+        (counts and index arithmetic only; device tables not built by ``grow``
+        are built from the chunk's arrays on their next use)."""
+        if chunk.U != self.U or chunk.G != self.G or chunk.depth != self.depth:
+            raise ValueError("the grown trees do not fit this stack (users, groups or depth)")
+        self._chunks.append(chunk)
+        self._grown_feature = max(self._grown_feature, int(max_feature))
+        self._arrays = None
+
+    def grow(self, chunk, device, D, max_feature):
+        """Append one fit call's trees (a GrownTrees on ``device``): their lane
+        tables go straight behind the existing ones (the table doubles when
+        full), tree_ids and group_offsets are rebuilt from the tree counts and
+        uploaded again.  Other (device, D) tables are dropped and rebuilt on
+        their next use."""
+        import torch
+
+        if not chunk.active.any():
+            return
+        key = (torch.device(device), int(D))
+        s = self._device_state(device, D)
+        self._dev = {key: s}
+        table, used = s["table"], s["used"]
+        if used + chunk.T > table.shape[1]:
+            grown = torch.zeros((2, max(2 * table.shape[1], used + chunk.T), 64, 2), dtype=torch.int32, device=key[0])
+            grown[:, :used] = table[:, :used]
+            table = grown
+        table[:, used:used + chunk.T] = self._lane_rows(chunk.out["nodes"], chunk.out["leaves"], chunk.T, self.depth, D,
+                                                         key[0])
+        self.attach(chunk, max_feature)
+        ids, goff, TT = self._logical()
+        s.update(table=table, used=TT, ids=torch.from_numpy(ids).to(key[0]), goff=torch.from_numpy(goff).to(key[0]),
+                 L=int(ids.shape[0]))
 
 
 def stack_forests(base, models):

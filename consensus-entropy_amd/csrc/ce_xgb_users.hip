@@ -10,8 +10,6 @@
 
 using namespace ce;
 
-extern "C" size_t ce_xgb_lds_bytes(int32_t D, int32_t G);
-
 // What the two entry points check alike.
 static int xgb_users_check(const void* X, ce_dtype x_dt, int64_t F, int32_t D, int64_t ld, const uint32_t* table,
                            int32_t TT, const int32_t* tree_ids, int64_t L, const int32_t* group_offsets, int32_t G,
@@ -31,31 +29,6 @@ static int xgb_users_check(const void* X, ce_dtype x_dt, int64_t F, int32_t D, i
     return CE_OK;
 }
 
-static size_t xgb_users_lds(int D, int G) { return ce_xgb_lds_bytes(D, G) + kXgbUsersExtraLds; }
-
-// One block per 64 rows of X: a well-formed geometry names at most F positions,
-// so a share is one tile (two where it straddles two users); the kernel divides
-// the real count, which only the device knows, among the blocks launched.
-static unsigned xgb_users_grid(int64_t F) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((F + kXgbTile - 1) / kXgbTile, 1 << 20));
-}
-
-template <class K, class... Args>
-static void xgb_users_launch(K kern, int64_t F, int D, int G, int S, ce_stream_t stream, Args... args) {
-    const size_t lds = xgb_users_lds(D, G);
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(xgb_users_grid(F)), dim3(64 * G * S), lds, (hipStream_t)stream, args...);
-}
-
-// f(kf) with the staging width of D as a compile-time value (k_xgb_lanes' ladder)
-template <class Fn>
-static void with_kf(int D, Fn&& fn) {
-    if (D <= 128) fn(std::integral_constant<int, 2>());
-    else if (D <= 256) fn(std::integral_constant<int, 4>());
-    else if (D <= 320) fn(std::integral_constant<int, 5>());
-    else fn(std::integral_constant<int, 8>());
-}
-
 extern "C" int ce_xgb_predict_proba_users(const void* X, ce_dtype x_dt, int64_t F, int32_t D, int64_t ld,
                                           const uint32_t* table, int32_t TT, const int32_t* tree_ids, int64_t L,
                                           const int32_t* group_offsets, int32_t G, int32_t depth, float base_margin,
@@ -71,7 +44,7 @@ extern "C" int ce_xgb_predict_proba_users(const void* X, ce_dtype x_dt, int64_t 
     if (ld_out < C) return fail(CE_EINVAL, "ld_out=%lld below the %d classes", (long long)ld_out, C);
     if (F > 0 && !out) return fail(CE_EINVAL, "null pointer");
     if (F == 0) return CE_OK;
-    const int S = std::max(1, 16 / G);
+    const int S = xgb_users_splits(G);
     const XgbArgs a{X, F, D, ld, G, C, S, base_margin, out, ld_out};
     const uint2* tb = reinterpret_cast<const uint2*>(table);
     const UsersGeom ug{item_offsets, frame_offsets, frame_perm, excl, U};
@@ -109,7 +82,7 @@ extern "C" int ce_xgb_score_users(const void* X, ce_dtype x_dt, int64_t F, int32
         return fail(CE_ELAUNCH, "ce_xgb_score_users: %s", hipGetErrorString(e));
     }
     if (F == 0) return CE_OK;
-    const int S = std::max(1, 16 / G);
+    const int S = xgb_users_splits(G);
     const XgbArgs a{X, F, D, ld, G, C, S, base_margin, nullptr, 0};
     const uint2* tb = reinterpret_cast<const uint2*>(table);
     const UsersGeom ug{item_offsets, frame_offsets, frame_perm, excl, U};

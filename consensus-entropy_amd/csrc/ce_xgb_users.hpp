@@ -31,6 +31,8 @@
 // rows and tree_ids -- sharing their text changed the code of k_xgb_walk and
 // k_xgb_lanes -- and the tests hold the two to the same bits.
 #pragma once
+#include <algorithm>
+
 #include "ce_members_users.hpp"  // UsersGeom, users_runs, users_frame, ScoreCounts, np_argmax
 #include "ce_xgb_walk.hpp"
 
@@ -231,6 +233,14 @@ __device__ __forceinline__ void users_proba(const float* mg, int G, int lane, fl
 // ce_xgb_lds_bytes), then the tile's rows [64] and the score finish's counters
 constexpr int kXgbUsersExtraLds = 64 * (int)sizeof(int64_t) + kXgbMaxGroups * kXgbMaxGroups * (int)sizeof(int);
 
+// A finish that declares `using takes_margins = void` is handed the margins
+// themselves, before the objective's transform (the fit's start margins,
+// ce_xgb_fit.hpp): fin.margins(mg, G, lane, q) for the frame at CSR position q.
+template <class Fin, class = void>
+struct fin_takes_margins : std::false_type {};
+template <class Fin>
+struct fin_takes_margins<Fin, typename Fin::takes_margins> : std::true_type {};
+
 // The body: the users walk, one tile after another, with a finish `fin`:
 //   fin.restage(u)      the block moves to user u (every thread, behind a barrier)
 //   fin.row(p, C, row)  one frame's probabilities (wave 0, the lane of the frame)
@@ -299,9 +309,13 @@ __device__ __forceinline__ void xgb_users(const XgbArgs& a, const XgbUsersForest
             if (w == 0) {
                 const int64_t ro = rowl[lane];
                 if (ro >= 0) {
-                    float pr[kXgbMaxGroups];
-                    users_proba(mg, a.G, lane, pr);
-                    fin.row(pr, a.C, ro);
+                    if constexpr (fin_takes_margins<Fin>::value) {
+                        fin.margins(mg, a.G, lane, q0 + lane);
+                    } else {
+                        float pr[kXgbMaxGroups];
+                        users_proba(mg, a.G, lane, pr);
+                        fin.row(pr, a.C, ro);
+                    }
                 }
             }
         }
@@ -373,6 +387,42 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     int* lcm = reinterpret_cast<int*>(xsm + a.D * kXgbCol + a.G * 64 + 16 + 128);  // behind the tile's rows
     XgbScoreFin fin{o, {lcm, o.cm, a.C * a.C, -1}, a.G};
     xgb_users<XDT, KF>(a, XgbUsersForests{table, tree_ids, group_offsets, TT, depth, L}, ug, fin);
+}
+
+}  // namespace ce
+
+// ---- the launch shape, shared by every TU that launches this walk -------------------
+// (ce_xgb_users.hip: predict and score; ce_xgb_fit.hip: the fit's start margins)
+extern "C" size_t ce_xgb_lds_bytes(int32_t D, int32_t G);
+
+namespace ce {
+
+// waves per group: fill a 16-wave block
+inline int xgb_users_splits(int G) { return std::max(1, 16 / G); }
+
+inline size_t xgb_users_lds(int D, int G) { return ce_xgb_lds_bytes(D, G) + kXgbUsersExtraLds; }
+
+// One block per 64 rows of X: a well-formed geometry names at most F positions,
+// so a share is one tile (two where it straddles two users); the kernel divides
+// the real count, which only the device knows, among the blocks launched.
+inline unsigned xgb_users_grid(int64_t F) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((F + kXgbTile - 1) / kXgbTile, 1 << 20));
+}
+
+template <class K, class... Args>
+inline void xgb_users_launch(K kern, int64_t F, int D, int G, int S, ce_stream_t stream, Args... args) {
+    const size_t lds = xgb_users_lds(D, G);
+    if (lds > 65536) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3(xgb_users_grid(F)), dim3(64 * G * S), lds, (hipStream_t)stream, args...);
+}
+
+// f(kf) with the staging width of D as a compile-time value (k_xgb_lanes' ladder)
+template <class Fn>
+inline void with_kf(int D, Fn&& fn) {
+    if (D <= 128) fn(std::integral_constant<int, 2>());
+    else if (D <= 256) fn(std::integral_constant<int, 4>());
+    else if (D <= 320) fn(std::integral_constant<int, 5>());
+    else fn(std::integral_constant<int, 8>());
 }
 
 }  // namespace ce

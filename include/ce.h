@@ -447,7 +447,7 @@ int ce_xgb_expf(const float *x, int64_t n, float *y, ce_stream_t stream);
  * The users form of the XGBoost member (SURVEY.md §8(f)5b / 5c;
  * csrc/ce_xgb_users.hpp, entries in csrc/ce_xgb_users.hip): after epoch 0 every
  * user's forest is the shared pretrained trees plus the rounds that user's own
- * mod.fit(xgb_model=) appended (amg_test.py:507; the refit stays on the host),
+ * mod.fit(xgb_model=) appended (amg_test.py:507; ce_xgb_fit_users grows them),
  * and one launch has every frame row of X predicted by the forest of the user
  * who owns it.  Depth <= 5 only (lane tables).
  *   table         [2][TT][64][2] u32: TT perfect trees of one common `depth`,
@@ -496,6 +496,84 @@ int ce_xgb_score_users(const void *X, ce_dtype x_dt, int64_t F, int32_t D, int64
                        const int64_t *frame_offsets, const int64_t *frame_perm_or_null,
                        const uint32_t *excl_or_null, const int32_t *y, int64_t *cm, int32_t *pred_or_null,
                        float *proba_or_null, int64_t ld_proba, ce_stream_t stream);
+
+/*
+ * The XGBoost member's refit on the device (csrc/ce_xgb_fit.hpp, entries in
+ * csrc/ce_xgb_fit.hip) -- replaces amg_test.py:507 for U users in one call:
+ *   mod.fit(X_batch.values, y_batch_enc, xgb_model=mod.get_booster())
+ * `rounds` boosting rounds of XGBClassifier(max_depth) are grown on every
+ * user's batch on top of that user's current forest: objective multi:softprob,
+ * tree_method exact (grow_colmaker on dense columns, one thread), gamma = alpha
+ * = 0, max_delta_step 0, no subsampling, no sample weights.  xgboost's C++ core
+ * is in no image of this project: the arithmetic below, restated row by row in
+ * tests/xgb_fit_ref.py, is the contract (matched bit for bit); parity with
+ * xgboost 1.3.3 itself is unpinned.
+ *   batch      user u's rows are rows[row_offsets[u] .. row_offsets[u + 1]) of
+ *              X [F, D] (x_dt F32 | F64, cast to float32 like DMatrix), of class
+ *              labels[i] in [0, G); R = row_offsets[U] rows in all, none of a
+ *              user more than n_max (HOST numbers).  DEVICE memory.
+ *   forests    table, TT, tree_ids, L, group_offsets, G, depth, base_margin: the
+ *              users' current stacked forests, as ce_xgb_predict_proba_users
+ *              takes them (G = C groups).
+ *   margins    m[i][k], float32: base_margin plus the leaves of the user's trees
+ *              of group k, by the users walk itself;
+ *   per round  every row's G gradients from the round's starting margins:
+ *              p = Softmax(m[i]) (fmaxf, glibc expf, a double wsum, / (float)
+ *              wsum), g = p[k] - (y == k), h = fmaxf(2.0f * p * (1.0f - p), 1e-16f);
+ *              then G trees, tree k from its own (g, h):
+ *   node       G, H: double sums of the float g, h over its rows in batch order;
+ *              weight = (float)(-G / (H + lambda)), root_gain = (float)(G * G /
+ *              (H + lambda));
+ *   search     per level, per feature in feature order, the rows sorted by the
+ *              feature ascending (stable by batch position) and scanned from
+ *              the high end; every open node keeps e = {double G, H; float last}.
+ *              For a row of node nid with value fv: when the node has seen a
+ *              row, fv != e.last and e.H >= min_child_weight, c = node - e and,
+ *              when c.H >= min_child_weight, loss_chg = (float)(gain(c) + gain(e)
+ *              - root_gain), gain(s) = s.G * s.G / (s.H + lambda) in double; the
+ *              candidate (loss_chg, f, (fv + e.last) * 0.5f) has c left, e
+ *              right.  Then the row is added to e and e.last = fv.  A candidate
+ *              replaces the node's best only when its loss_chg is finite and
+ *              strictly greater (the best starts at 0): the lower feature wins
+ *              an exact tie, within a feature the first of the scan.
+ *   expand     open nodes in id order: best loss_chg > 1e-6f splits the node
+ *              (children take the next two ids, left then right; rows with
+ *              x < cond go left; default_left set); otherwise, and for every
+ *              node still open after max_depth levels, a leaf of weight * eta;
+ *   update     m[i][k] += the leaf of the row, in float.
+ * Outputs, for tree (u * rounds + r) * G + k (round r, group k of user u), T =
+ * U * rounds * G slots in all -- a user without rows, or one flagged in
+ * status, leaves its slots unwritten:
+ *   nodes_out  [T][max(2^depth - 1, 1)][2] u32, leaves_out [T][2^depth] f32: the
+ *              packed perfect-tree form ce_xgb_lane_table reads, at the stack's
+ *              common `depth` (>= max_depth);
+ *   left_out, right_out, split_out [T][63] int32, cond_out [T][63] f32 (the leaf
+ *              value at a leaf), default_left_out [T][63] u8, num_nodes_out [T]:
+ *              the model's own node arrays (entries past num_nodes: -1, -1, 0,
+ *              0.0, 0);
+ *   margins_out_or_null [R, G] f32: the batch's final margins, by position.
+ *   status     [U] int32, only ever SET: 1 where a user's batch holds a value
+ *              that is not finite as float32, a row outside [0, F) or a label
+ *              outside [0, G) (its forest gets no tree), 2 where a batch holds
+ *              more than n_max rows (not run).  Zero it before the call.
+ * workspace: ce_xgb_fit_workspace_bytes(R, n_max, D, G, rounds) bytes, 16-byte
+ * aligned (the margins and every feature's sorted column: about 6 R D bytes).
+ * Before any launch -- CE_EINVAL: bad shapes, rounds or max_depth < 1, depth <
+ * max_depth, n_max > R, eta / lambda / min_child_weight out of range, a null
+ * pointer; CE_EUNSUPPORTED: D > 512, G > 8, G == 1 (binary:logistic), max_depth
+ * > 5, depth > 5, n_max > 4096 rows per user; CE_EWORKSPACE.  R == 0 launches
+ * nothing.  No allocation; stream-ordered, nothing read back.
+ */
+size_t ce_xgb_fit_workspace_bytes(int64_t R, int64_t n_max, int32_t D, int32_t G, int32_t rounds);
+int ce_xgb_fit_users(const void *X, ce_dtype x_dt, int64_t F, int32_t D, int64_t ld, const int64_t *rows,
+                     const int32_t *labels, const int64_t *row_offsets, int32_t U, int64_t R, int64_t n_max,
+                     const uint32_t *table, int32_t TT, const int32_t *tree_ids, int64_t L,
+                     const int32_t *group_offsets, int32_t G, int32_t depth, float base_margin,
+                     int32_t rounds, int32_t max_depth, float eta, float lambda, float min_child_weight,
+                     uint32_t *nodes_out, float *leaves_out, int32_t *left_out, int32_t *right_out,
+                     int32_t *split_out, float *cond_out, uint8_t *default_left_out, int32_t *num_nodes_out,
+                     float *margins_out_or_null, int32_t *status, void *workspace, size_t workspace_bytes,
+                     ce_stream_t stream);
 
 /*
  * glibc's f64 log as the engine evaluates it inside every entropy

@@ -1,0 +1,394 @@
+"""XGBClassifier(max_depth=5).fit(X_batch, y, xgb_model=booster) restated row by
+row: the boosting rounds the reference grows at amg_test.py:507 on its
+'classifier_xgb' member (deam_classifier.py:227-231), as xgboost 1.3.3's exact
+grower (grow_colmaker on dense columns, one thread) is read here.  xgboost's
+C++ core is in no image of this project, so this file IS the arithmetic
+contract of ce_xgb_fit_users (0 differing bits); parity with xgboost 1.3.3
+itself is unpinned (DESIGN.md §3 lists every choice, next to the predictor's).
+
+objective multi:softprob, eta 0.3f, lambda 1, alpha 0, gamma 0,
+min_child_weight 1, max_delta_step 0, no subsampling, tree_method exact.
+
+Every operation is a numpy float32 or Python float (IEEE double) scalar
+operation, or the C library's expf; sums run one term after the other.
+``brute_check`` recomputes every split of a grown tree from scratch."""
+import math
+
+import numpy as np
+
+from oracle.ce_oracle import libm_expf
+
+F32 = np.float32
+RT_EPS = F32(1e-6)      # kRtEps: the least loss_chg that splits a node
+MIN_HESS = F32(1e-16)   # multi:softprob's floor of the hessian
+MAX_NODES = 63          # a depth-5 tree
+
+
+def softmax_row(m):
+    """common::Softmax, as oracle/ce_oracle.c:ce_ref_xgb_predict_proba: fmaxf
+    maximum, expf, a double wsum, each e divided by (float)wsum."""
+    mx = m[0]
+    for v in m[1:]:
+        mx = F32(max(v, mx))
+    e = [libm_expf(F32(v - mx)) for v in m]
+    ws = 0.0
+    for v in e:
+        ws += float(v)
+    ws = F32(ws)
+    return [F32(v / ws) for v in e]
+
+
+def gradients(m, y):
+    """(g, h) float32 [n, C] from the margins m [n, C] and labels y [n]."""
+    n, C = m.shape
+    g, h = np.empty((n, C), F32), np.empty((n, C), F32)
+    for i in range(n):
+        p = softmax_row([m[i, k] for k in range(C)])
+        for k in range(C):
+            g[i, k] = F32(p[k] - (F32(1.0) if int(y[i]) == k else F32(0.0)))
+            h[i, k] = F32(max(F32(F32(F32(2.0) * p[k]) * F32(F32(1.0) - p[k])), MIN_HESS))
+    return g, h
+
+
+def gain(G, H, lam):
+    return G * G / (H + lam)
+
+
+def need_replace(best, loss_chg, f):
+    """SplitEntry::NeedReplace: a candidate replaces the best only when its
+    loss_chg is finite; an incumbent of a lower or the same feature only gives
+    way to a strictly greater loss_chg, one of a higher feature to an equal one."""
+    if not math.isfinite(float(loss_chg)):
+        return False
+    if best[1] <= f:
+        return bool(loss_chg > best[0])
+    return not bool(best[0] > loss_chg)
+
+
+def scan_order(X):
+    """Per feature, the batch rows in the order the backward scan meets them:
+    sorted by the feature ascending, stable by batch position, from the high end."""
+    return [np.argsort(X[:, f], kind="stable")[::-1] for f in range(X.shape[1])]
+
+
+def node_sums(g, h, pos, nid):
+    """double sums of the float g, h over the node's rows in batch order."""
+    G = H = 0.0
+    for i in range(len(pos)):
+        if pos[i] == nid:
+            G += float(g[i])
+            H += float(h[i])
+    return G, H
+
+
+TIES = {"feature": 0, "scan": 0}  # exact loss_chg ties met so far: between two features / within one feature's scan
+
+
+def grow_tree(X, order, g, h, max_depth, eta, lam, mcw, log=None):
+    """One tree from the gradients (g, h) [n] of its group.  Returns (tree, pos):
+    the XgbForest node arrays and each row's leaf.  ``log``: a list that takes,
+    per split node, (rows of the node, G, H, root_gain, chosen (loss_chg, f, cond), g, h)."""
+    n, D = X.shape
+    left, right, split, cond, dl = [-1], [-1], [0], [F32(0.0)], [0]
+    pos = np.zeros(n, np.int64)
+    is_open = [0]
+    lam, mcw, eta = float(F32(lam)), float(F32(mcw)), F32(eta)
+    for depth in range(max_depth + 1):
+        stats = {}
+        for nid in is_open:
+            G, H = node_sums(g, h, pos, nid)
+            stats[nid] = (G, H, F32(-G / (H + lam)), F32(gain(G, H, lam)))
+        if depth == max_depth:
+            for nid in is_open:
+                cond[nid] = F32(stats[nid][2] * eta)
+            break
+        best = {nid: (F32(0.0), 0, F32(0.0)) for nid in is_open}
+        for f in range(D):
+            e = {nid: [0.0, 0.0, F32(0.0), False] for nid in is_open}  # G, H, last, seen
+            for i in order[f]:
+                nid = int(pos[i])
+                if nid not in e:
+                    continue
+                fv, en = X[i, f], e[nid]
+                if en[3] and fv != en[2] and en[1] >= mcw:
+                    cG, cH = stats[nid][0] - en[0], stats[nid][1] - en[1]
+                    if cH >= mcw:
+                        loss_chg = F32(gain(cG, cH, lam) + gain(en[0], en[1], lam) - float(stats[nid][3]))
+                        if loss_chg == best[nid][0] and loss_chg > F32(0.0):
+                            TIES["scan" if best[nid][1] == f else "feature"] += 1
+                        if need_replace(best[nid], loss_chg, f):
+                            best[nid] = (loss_chg, f, F32(F32(fv + en[2]) * F32(0.5)))
+                en[0] += float(g[i])
+                en[1] += float(h[i])
+                en[2], en[3] = fv, True
+            # the end-of-column candidate (everything to the right) never fires on a dense
+            # column: its left side c = node - e holds no row, so c.H < min_child_weight
+        nxt = []
+        for nid in is_open:
+            lc, f, c = best[nid]
+            if lc > RT_EPS:
+                if log is not None:
+                    log.append((np.flatnonzero(pos == nid), stats[nid][0], stats[nid][1], stats[nid][3], best[nid], g, h))
+                l, r = len(left), len(left) + 1
+                for a, v in ((left, -1), (right, -1), (split, 0), (cond, F32(0.0)), (dl, 0)):
+                    a.extend([v, v])
+                left[nid], right[nid], split[nid], cond[nid], dl[nid] = l, r, f, c, 1
+                nxt += [l, r]
+            else:
+                cond[nid] = F32(stats[nid][2] * eta)
+        for i in range(n):
+            nid = int(pos[i])
+            if left[nid] != -1:
+                pos[i] = left[nid] if X[i, split[nid]] < cond[nid] else right[nid]
+        is_open = nxt
+        if not is_open:
+            break
+    tree = {"left": np.asarray(left, np.int32), "right": np.asarray(right, np.int32),
+            "split": np.asarray(split, np.int32), "cond": np.asarray(cond, F32),
+            "default_left": np.asarray(dl, np.uint8)}
+    return tree, pos
+
+
+def fit_rounds(X, y, margins, rounds, max_depth=5, eta=0.3, lam=1.0, mcw=1.0, log=None):
+    """``rounds`` boosting rounds on the batch X [n, D] (cast to float32, dense
+    and finite), labels y [n] in [0, C), start margins [n, C] float32.  Returns
+    (trees, tree_info, margins): rounds * C trees, round-major, group inside
+    the round, and the batch's final margins.  No row: no tree."""
+    X = np.ascontiguousarray(np.asarray(X, np.float64).astype(F32))
+    m = np.array(margins, F32)
+    n, C = m.shape
+    if n == 0:
+        return [], [], m
+    assert np.isfinite(X).all() and X.shape[0] == n
+    order = scan_order(X)
+    trees, info = [], []
+    for _ in range(rounds):
+        g, h = gradients(m, y)
+        for k in range(C):
+            tree, pos = grow_tree(X, order, g[:, k], h[:, k], max_depth, eta, lam, mcw, log)
+            for i in range(n):
+                m[i, k] = F32(m[i, k] + tree["cond"][pos[i]])
+            trees.append(tree)
+            info.append(k)
+    return trees, info, m
+
+
+def start_margins(X, forest):
+    """float32 [n, G]: base_margin plus the leaves of the forest's trees of each
+    group, in model order (the order the users walk adds them)."""
+    X = np.asarray(X, np.float64).astype(F32)
+    m = np.full((X.shape[0], forest.n_groups), forest.base_margin, F32)
+    for tr, k in zip(forest.trees, forest.tree_info):
+        for i in range(X.shape[0]):
+            nid = 0
+            while tr["left"][nid] != -1:
+                nid = tr["left"][nid] if X[i, tr["split"][nid]] < tr["cond"][nid] else tr["right"][nid]
+            m[i, k] = F32(m[i, k] + tr["cond"][nid])
+    return m
+
+
+def fit_forest(forest, X, y, rounds, max_depth=5, log=None, **kw):
+    """The forest after ``fit(X, y, xgb_model=forest)``: its trees, then the grown rounds; and the final margins."""
+    from ce_amd.xgb import XgbForest
+
+    trees, info, m = fit_rounds(X, y, start_margins(X, forest), rounds, max_depth, log=log, **kw)
+    out = XgbForest(list(forest.trees) + trees, list(forest.tree_info) + info, forest.num_class, forest.base_score,
+                    forest.objective, forest.num_feature)
+    return out, m
+
+
+def tree_json(tr, num_feature):
+    """One grown tree in xgboost's JSON schema (what continued_model appends)."""
+    n = int(tr["left"].size)
+    return {"tree_param": {"num_nodes": str(n), "num_feature": str(num_feature), "size_leaf_vector": "0",
+                           "num_deleted": "0"},
+            "id": 0, "left_children": tr["left"].tolist(), "right_children": tr["right"].tolist(),
+            "parents": [2147483647] + [0] * (n - 1), "split_indices": tr["split"].tolist(),
+            "split_conditions": [float(v) for v in tr["cond"]], "default_left": [bool(v) for v in tr["default_left"]],
+            "loss_changes": [0.0] * n, "sum_hessian": [1.0] * n, "base_weights": [0.0] * n}
+
+
+def rounds_model(base_model, trees, info):
+    """The grown rounds as a JSON model of their own (continued_model's ``more``)."""
+    import copy
+
+    out = copy.deepcopy(base_model)
+    m = out["learner"]["gradient_booster"]["model"]
+    nf = int(out["learner"]["learner_model_param"].get("num_feature", "0"))
+    m["trees"] = [dict(tree_json(t, nf), id=i) for i, t in enumerate(trees)]
+    m["tree_info"] = [int(k) for k in info]
+    m["gbtree_model_param"]["num_trees"] = str(len(trees))
+    return out
+
+
+def brute_check(X, entry, lam=1.0, mcw=1.0):
+    """The independent check of one split node (``entry`` of grow_tree's log):
+    for every feature and every threshold between two distinct values of the
+    node's rows, the right side summed afresh in scan order, the left side as
+    node minus right; the best by the tie rule, the features taken in
+    DESCENDING order (so the ``!(best > new)`` half of the rule decides the
+    ties between features).  Returns the (loss_chg, f, cond) it finds."""
+    X = np.asarray(X, np.float64).astype(F32)
+    rows, G, H, root_gain, _, g, h = entry
+    lam, mcw = float(F32(lam)), float(F32(mcw))
+    inside = set(int(i) for i in rows)
+    best = (F32(0.0), 0, F32(0.0))
+    for f in range(X.shape[1] - 1, -1, -1):
+        seq = [int(i) for i in np.argsort(X[:, f], kind="stable")[::-1] if int(i) in inside]
+        own = (F32(0.0), f, F32(0.0))  # within the feature: the first of the descending scan wins a tie
+        for cut in range(1, len(seq)):
+            hi, lo = X[seq[cut - 1], f], X[seq[cut], f]
+            if hi == lo:
+                continue
+            eG = eH = 0.0
+            for i in seq[:cut]:
+                eG += float(g[i])
+                eH += float(h[i])
+            cG, cH = G - eG, H - eH
+            if eH < mcw or cH < mcw:
+                continue
+            lc = F32(gain(cG, cH, lam) + gain(eG, eH, lam) - float(root_gain))
+            if math.isfinite(float(lc)) and lc > own[0]:
+                own = (lc, f, F32(F32(lo + hi) * F32(0.5)))
+        if own[0] > F32(0.0) and need_replace(best, own[0], f):
+            best = own
+    return best
+
+
+def batch(n, D, C, kind="ties", seed=0):
+    """A batch (X f64 [n, D], y [n]) of the parity tests.  Every kind has
+    feature 0 quantised to four values, q and 3 - q on rows 2 j and 2 j + 1 of
+    one label (mirrored class counts: exact loss_chg ties within the scan from
+    uniform margins), and the last column a copy of it when D > 1 (exact ties
+    between two features); the labels follow the features, so trees grow deep.
+      ties     further columns rounded to one decimal (many equal values)
+      const    one constant column
+      single   one label only
+      lacking  the last class absent from the batch
+      mirror   the labels are the pairs' alone (the mirrored counts hold for every class)
+      hand     the hand-worked shape: column 0 counts the rows, the upper half is class 1"""
+    rng = np.random.default_rng(seed)
+    X = rng.normal(size=(n, D))
+    q = rng.integers(0, 4, (n + 1) // 2)
+    X[:, 0] = np.where(np.arange(n) % 2 == 0, q[np.arange(n) // 2], 3 - q[np.arange(n) // 2]).astype(np.float64)
+    yj = rng.integers(0, C, (n + 1) // 2)
+    y = yj[np.arange(n) // 2]
+    if D > 2:
+        rule = (np.floor(2.0 * X[:, 1]).astype(np.int64) + (X[:, D // 2] > 0)) % C
+        y = y if kind == "mirror" else np.where(rng.random(n) < 0.5, rule, y)
+        X[:, 1:D - 1] = np.round(X[:, 1:D - 1], 1) if kind == "ties" else X[:, 1:D - 1]
+    if D > 1:
+        X[:, D - 1] = X[:, 0]
+    if kind == "const" and D > 2:
+        X[:, D // 2] = 1.25
+    if kind == "single":
+        y = np.full(n, 1)
+    if kind == "lacking":
+        y = y % (C - 1)
+    if kind == "hand":
+        X[:, 0] = np.arange(n)
+        y = (2 * np.arange(n) >= n).astype(np.int64)
+    return X, y.astype(np.int64)
+
+
+def same_tree(a, b):
+    return all(np.array_equal(np.asarray(a[k]), np.asarray(b[k])) for k in ("left", "right", "split", "default_left")) \
+        and np.array_equal(np.asarray(a["cond"], F32).view(np.uint32), np.asarray(b["cond"], F32).view(np.uint32))
+
+
+# ---- what the kernel writes, and the inputs the CPU and GPU tests share -------------
+def expected_outputs(per_user, U, rounds, G, depth):
+    """ce_xgb_fit_users' outputs as numpy arrays, from every user's grown trees
+    (``per_user[u]``: rounds * G trees in model order, or an empty list): slot
+    (u rounds + r) G + k; the slots of a user without trees stay as the wrapper
+    allocates them (zero, children -1)."""
+    from ce_amd.xgb import XgbForest
+
+    T, NI, NL = U * rounds * G, max((1 << depth) - 1, 1), 1 << depth
+    out = {"nodes": np.zeros((T, NI, 2), np.uint32), "leaves": np.zeros((T, NL), F32),
+           "left": np.full((T, MAX_NODES), -1, np.int32), "right": np.full((T, MAX_NODES), -1, np.int32),
+           "split": np.zeros((T, MAX_NODES), np.int32), "cond": np.zeros((T, MAX_NODES), F32),
+           "default_left": np.zeros((T, MAX_NODES), np.uint8), "num_nodes": np.zeros(T, np.int32)}
+    for u, trees in enumerate(per_user):
+        for j, tr in enumerate(trees):
+            t, n = u * rounds * G + j, tr["left"].size
+            nodes, leaves, _, _ = XgbForest([tr], [0], G, 0.5, "multi:softprob", 0).pack(depth)
+            out["nodes"][t], out["leaves"][t], out["num_nodes"][t] = nodes[0], leaves[0], n
+            for k in ("left", "right", "split", "cond", "default_left"):
+                out[k][t, :n] = tr[k]
+    return out
+
+
+def grown_chunk(per_user, U, rounds, G, depth, device="cpu"):
+    """The ``ce_amd.xgb.GrownTrees`` a fit that grew ``per_user`` hands to the stack."""
+    import torch
+
+    from ce_amd.xgb import GrownTrees
+
+    out = expected_outputs(per_user, U, rounds, G, depth)
+    t = {k: torch.from_numpy(v.view(np.int32) if v.dtype == np.uint32 else v).to(device) for k, v in out.items()}
+    return GrownTrees(t, U, rounds, G, depth, [len(p) > 0 for p in per_user])
+
+
+# name: D, C, rounds, max_depth, each user's rows, each user's kind of batch, base rounds (0: leaves only,
+# so every row starts from the same margins), X as float64
+CASES = {
+    "deep":    dict(D=5, C=4, rounds=3, max_depth=5, rows=(130, 0, 65), kinds=("ties", "ties", "const"), base=2, f64=True),
+    "tiny":    dict(D=1, C=3, rounds=1, max_depth=1, rows=(6, 1, 7), kinds=("hand", "hand", "hand"), base=0, f64=False),
+    "wide":    dict(D=70, C=3, rounds=1, max_depth=3, rows=(65, 7, 130), kinds=("single", "lacking", "ties"), base=2,
+                    f64=True),
+    "uniform": dict(D=5, C=4, rounds=1, max_depth=3, rows=(130, 6, 0), kinds=("mirror", "ties", "ties"), base=0, f64=False),
+}
+_CACHE = {}
+
+
+def case(name):
+    """The inputs of a parity case, and what the restatement grows from them
+    (computed once).  A dict: base (JSON), X [F, D] (rows no user owns
+    included), rows / labels / row_offsets (every user's rows in a shuffled
+    order, stacked), per_user (grown trees), info, margins (final, stacked),
+    forests (each user's XgbForest after the fit)."""
+    if name in _CACHE:
+        return _CACHE[name]
+    from ce_amd.xgb import XgbForest, synthetic_model
+
+    c = dict(CASES[name])
+    D, C, U = c["D"], c["C"], len(c["rows"])
+    rng = np.random.default_rng(sum(map(ord, name)))
+    if c["base"]:
+        base = synthetic_model(n_rounds=c["base"], num_class=C, max_depth=3, num_feature=D, seed=11)
+    else:
+        base = synthetic_model(n_rounds=1, num_class=C, max_depth=0, num_feature=D, seed=11)
+    forest = XgbForest.from_json(base)
+    F = sum(c["rows"]) + 7
+    X = rng.normal(size=(F, D))
+    perm = rng.permutation(F)
+    rows, labels, off, at = [], [], [0], 0
+    per_user, margins, forests = [], [], []
+    for u, n in enumerate(c["rows"]):
+        r = perm[at:at + n]
+        at += n
+        Xu, yu = batch(n, D, C, c["kinds"][u], seed=100 + u)
+        X[r] = Xu
+        if not c["f64"]:
+            X = X.astype(F32).astype(np.float64)
+        rows.append(r)
+        labels.append(yu)
+        off.append(off[-1] + n)
+        after, m = fit_forest(forest, X[r], yu, c["rounds"], c["max_depth"])
+        per_user.append(after.trees[len(forest.trees):])
+        margins.append(m)
+        forests.append(after)
+    c.update(base=base, forest=forest, X=X, U=U, counts=tuple(c["rows"]), rows=np.concatenate(rows).astype(np.int64),
+             labels=np.concatenate(labels).astype(np.int32), row_offsets=np.asarray(off, np.int64),
+             per_user=per_user, margins=np.concatenate(margins), forests=forests,
+             info=[k for _ in range(c["rounds"]) for k in range(C)])
+    _CACHE[name] = c
+    return c
+
+
+def full_model(base, trees, info):
+    """The JSON model after the fit: ``continued_model`` of the base and the grown rounds."""
+    from ce_amd.xgb import continued_model
+
+    return continued_model(base, rounds_model(base, trees, info)) if trees else base
