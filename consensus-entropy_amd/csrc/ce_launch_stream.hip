@@ -1,5 +1,7 @@
 // ce_launch_stream.hip -- the streaming stage-1 launcher (the only TU that
 // instantiates k_stream_nmc / k_stream_direct / k_stream_wide2 / k_stream_wide).
+#include <atomic>
+
 #include "ce_dispatch.hpp"
 #include "ce_stream.hpp"
 #include "ce_wide_stream.hpp"
@@ -29,6 +31,8 @@ static inline StreamArgs stream_args(const CommArgs& a, int G, int64_t base_idx)
     s.vote = nullptr;
     s.vote_heavy = 0;
     s.seed = nullptr;
+    s.claim = nullptr;
+    s.claim_from = 0;
     return s;
 }
 
@@ -62,6 +66,48 @@ static inline void with_unr(int unr, F&& f) {
 
 static int launch_stream_impl(const CommArgs& a, int G, int q, int64_t base_idx, WsLists w, hipStream_t st,
                               const uint32_t* excl, const FoldOut* fold);
+
+// Ordered tile claims (k_stream_nmc, ce_stream.hpp): the share of the pool, in
+// thousandths, that the waves claim from the workspace's claim word instead of
+// taking it grid-cyclically.  The claimed part is the END of the pool: the
+// fast waves take more of it, so the launch no longer ends with its slowest
+// waves alone on the chip.  It has to cover the waves' spread (the slowest
+// wave's static share must end before the pool does: 6 % measured) and costs a
+// ring drain per claimed unit.  Pools with fewer than CE_STREAM_CLAIM_MIN_ROUNDS
+// tiles per wave keep the static order.  Share and gate are measured on the f32
+// [N,16,4] kernel alone (profiles/stream_claims_ab.json), so only that kernel
+// claims; the other two-slot item-major kernels (bf16, C = 8) are unmeasured
+// and keep the static order.
+#ifndef CE_STREAM_CLAIM_PERMILLE
+#define CE_STREAM_CLAIM_PERMILLE 150
+#endif
+#ifndef CE_STREAM_CLAIM_MIN_ROUNDS
+#define CE_STREAM_CLAIM_MIN_ROUNDS 300
+#endif
+// Process-wide overrides (< 0: the build's value) and the last launch's decision,
+// for the tests and the diagnostic tools: ce_debug_stream_claims() below.  Not
+// part of include/ce.h.
+static std::atomic<int64_t> g_claim_permille{-1}, g_claim_min_rounds{-1}, g_claim_from_last{0};
+extern "C" void ce_debug_stream_claims(int64_t permille, int64_t min_rounds) {
+    g_claim_permille = permille;
+    g_claim_min_rounds = min_rounds;
+}
+// claim_from of the calling process's last k_stream_nmc launch (0: static order)
+extern "C" int64_t ce_debug_stream_claim_from() { return g_claim_from_last; }
+
+// the static grid-cyclic rounds (tiles per wave) before the first claimed tile
+// (>= 4: the first claim goes out two positions before its use, behind the two
+// positions issued ahead of the loop); 0: no claims for this pool
+static inline int64_t claim_from(int64_t N, int grid) {
+    int64_t permille = g_claim_permille, min_rounds = g_claim_min_rounds;
+    if (permille < 0) permille = CE_STREAM_CLAIM_PERMILLE;
+    if (min_rounds < 0) min_rounds = CE_STREAM_CLAIM_MIN_ROUNDS;
+    if (permille > 1000) permille = 1000;
+    const int64_t rounds = cdiv(N, 64) / ((int64_t)grid * 4);  // whole grid-cyclic rounds in the pool
+    if (rounds < min_rounds || permille == 0) return 0;
+    const int64_t r = rounds - cdiv(rounds * permille, 1000);
+    return r < 4 ? 4 : r;
+}
 
 // the LDS-DMA loads' cache-policy bits (2: non-temporal -- the pool is read once)
 #ifndef CE_NMC_AUX
@@ -110,6 +156,12 @@ static int launch_stream_impl(const CommArgs& a, int G, int q, int64_t base_idx,
         note_kernel("ce::k_stream_nmc<%d, %d, %d, %d, %s, %d>", DT_, C_, S_, AUX_, MNC_ ? "true" : "false", \
                     RING_);                                                                               \
         stream_grid(sa, grid);                                                                            \
+        g_claim_from_last = 0;                                                                            \
+        if (fold && !MNC_ && RING_ == 2 && DT_ == kF32 && C_ == 4 && CE_STREAM_CLAIM_K > 0) {             \
+            sa.claim_from = claim_from(a.N, grid); /* ordered claims (ce_stream.hpp) */                   \
+            sa.claim = sa.claim_from > 0 ? w.ctr + kWsClaimSlot : nullptr;                                \
+            g_claim_from_last = sa.claim_from;                                                            \
+        }                                                                                                 \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, sa, q, w.c);                               \
         return folded;                                                                                    \
     }
@@ -233,3 +285,15 @@ static int launch_stream_impl(const CommArgs& a, int G, int q, int64_t base_idx,
     if (rc != CE_OK || rc_excl != CE_OK) return 0;
     return wide_folded ? 2 : 1;
 }
+
+#ifdef CE_STREAM_STAMPS
+// diagnostic build only: the last k_stream_nmc launch's per-wave stamps (ce_stream.hpp)
+extern "C" int ce_debug_stream_stamps(uint64_t* host, int waves) {
+    if (waves < 0 || waves > kStampWaves) return -1;
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stream_stamps), (size_t)waves * kStampCols * sizeof(uint64_t)) ==
+                   hipSuccess
+               ? 0
+               : -1;
+}
+extern "C" int ce_debug_stream_stamp_cols() { return kStampCols; }
+#endif

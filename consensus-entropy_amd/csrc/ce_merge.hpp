@@ -285,9 +285,13 @@ __device__ inline void merge_lists_lean(Src src, int nl, int q, WaveListsT<W>& L
 
 template <int W>
 __device__ inline void fold_merge(uint32_t* ctr, double* oval, int64_t* oidx, Cand* ocand, int q, const Cand* wc0,
-                                  WaveListsT<W>& L, const Cand* extra = nullptr) {
+                                  WaveListsT<W>& L, const Cand* extra = nullptr, uint32_t* claim = nullptr) {
     __shared__ LeanMergeSmem<W> ms;
     if (!arrive_last(ctr, gridDim.x, &ms.ticket)) return;  // block-uniform
+    // claim: the grid's tile-claim word (k_stream_nmc).  Every block has arrived,
+    // so every claim of the launch has returned: back to zero for the next launch
+    // (write-through, like the lists)
+    if (claim && threadIdx.x == 0) __hip_atomic_store(claim, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // extra (a chunked job's running list) may be ocand itself: every input is
     // read before the outputs are written (barriers in between)
     const int nl = (int)gridDim.x + (extra ? 1 : 0);

@@ -34,6 +34,15 @@ constexpr int64_t kSortMinChunk = 1024;  // items per wave at least (16 steps)
 
 constexpr int kWsCounters = 16384;
 constexpr size_t kWsHeader = (size_t)kWsCounters * sizeof(uint32_t);  // 64 KiB
+// Who uses which word.  Word 0 is the arrival ticket of every folded launch
+// (fold_merge: the streaming, wide and frames kernels; launches that share a
+// workspace run one after another on one stream).  The LAST word is the
+// streaming kernel's tile-claim word (k_stream_nmc, ce_stream.hpp): waves add to
+// it while they stream and the launch's last block stores it back to zero.  It
+// is never a ticket: a new ticket user takes a word below kWsClaimSlot, and a
+// new claim-like word takes a slot of its own, a cache line (32 words) away
+// from every other one.
+constexpr int kWsClaimSlot = kWsCounters - 1;
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
