@@ -33,7 +33,9 @@
 // each walking the pass's threads serially), the node statistics (one thread
 // per open node over all rows) and the rank sort (n^2 / 8 loads per thread,
 // 2 M at the 4096-row cap, which itself is only what the LDS holds) have no
-// measurement of their own; batches near the cap are untimed.
+// measurement of their own; batches near the cap are untimed.  Their bits are
+// tested (tests/test_gpu_xgb_fit_edges.py: 4095 and 4096 rows, and 4096 rows x
+// 512 features, the largest LDS the entry accepts).
 #pragma once
 #include "ce_xgb_users.hpp"
 

@@ -1,7 +1,8 @@
 """The on-device XGBoost refit's arithmetic contract (tests/xgb_fit_ref.py) on
 the CPU: the row-loop restatement against its own brute-force split search,
 against the oracle predictor, against one hand-worked case, and the guards that
-keep the parity inputs of tests/test_gpu_xgb_fit.py from being vacuous."""
+keep the parity inputs of tests/test_gpu_xgb_fit.py and
+tests/test_gpu_xgb_fit_edges.py from being vacuous."""
 import numpy as np
 import pytest
 
@@ -13,7 +14,11 @@ from xgb_users_ref import bits
 F32 = np.float32
 
 
-@pytest.mark.parametrize("name", sorted(R.CASES))
+# brute_check is quadratic in a node's rows: the edge cases of at most 300 rows ("d512" takes 6 s of it)
+EDGE_BRUTE = [n for n, c in R.EDGE_CASES.items() if max(c["rows"]) <= 300]
+
+
+@pytest.mark.parametrize("name", sorted(R.CASES) + EDGE_BRUTE)
 def test_restatement_equals_its_brute_force_check(name):
     """Every split node of every grown tree: the best (loss_chg, feature,
     threshold) found by summing each candidate's right side afresh, features in
@@ -22,13 +27,13 @@ def test_restatement_equals_its_brute_force_check(name):
     checked = 0
     for u in range(c["U"]):
         r = c["rows"][c["row_offsets"][u]:c["row_offsets"][u + 1]]
-        if r.size == 0:
+        if r.size == 0 or c["status"][u]:
             continue
         log = []
         R.fit_forest(c["forest"], c["X"][r], c["labels"][c["row_offsets"][u]:c["row_offsets"][u + 1]], c["rounds"],
-                     c["max_depth"], log=log)
+                     c["max_depth"], log=log, **c["kw"])
         for entry in log:  # every split node of every grown tree
-            lc, f, cond = R.brute_check(c["X"][r], entry)
+            lc, f, cond = R.brute_check(c["X"][r], entry, **{k: v for k, v in c["kw"].items() if k != "eta"})
             assert (bits(lc), f, bits(cond)) == (bits(entry[4][0]), entry[4][1], bits(entry[4][2])), (name, u)
             checked += 1
     assert checked > 0
@@ -178,6 +183,69 @@ def test_parity_inputs_are_not_vacuous():
         assert max(depths) == c["max_depth"], (name, max(depths))
     assert 2 * n_split >= n_trees, (n_split, n_trees)
     assert R.TIES["feature"] > 0 and R.TIES["scan"] > 0, R.TIES
+
+
+def _levels(t):
+    """The depth of every node of a tree (children follow their parent in the arrays)."""
+    lev = np.zeros(t["left"].size, np.int64)
+    for nid in range(t["left"].size):
+        if t["left"][nid] != -1:
+            lev[t["left"][nid]] = lev[t["right"][nid]] = lev[nid] + 1
+    return lev
+
+
+def _split_features(c):
+    return {int(f) for p in c["per_user"] for t in p for f, l in zip(t["split"], t["left"]) if l != -1}
+
+
+def test_edge_inputs_are_not_vacuous():
+    """Asserted on the restatement alone: the inputs of tests/test_gpu_xgb_fit_edges.py
+    reach what they are there for (the 4096-row, 512-feature case apart: its
+    one level is all it is there for)."""
+    import warnings
+
+    cases = {n: R.case(n) for n in R.EDGE_CASES if n != "d512cap" and n not in R.PARAM_CASES}
+    # the parameter cases afresh: no warning, finite margins, both kinds of exact tie
+    R.TIES.update(feature=0, scan=0)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        for n in R.PARAM_CASES:
+            R._CACHE.pop(n, None)
+            cases[n] = c = R.case(n)
+            assert np.isfinite(c["margins"]).all(), n
+            trees = c["per_user"][0]
+            assert 2 * sum(t["left"].size > 1 for t in trees) >= len(trees), n
+    assert R.TIES["feature"] > 0 and R.TIES["scan"] > 0, R.TIES
+    # lambda = 0 on hessians that cancel: candidates of infinite loss_chg are met and skipped, the margins stay finite
+    R.SKIPPED["non_finite"] = 0
+    R._CACHE.pop("steep", None)
+    cases["steep"] = R.case("steep")
+    assert R.SKIPPED["non_finite"] > 0 and np.isfinite(cases["steep"]["margins"]).all()
+    assert all(t["left"].size > 1 for t in cases["steep"]["per_user"][0])
+    # a full tree: 63 nodes, 16 of them on level 4 (two scans of 8 slots), 32 leaves on level 5
+    full = [(t, _levels(t)) for p in cases["full"]["per_user"] for t in p if t["left"].size == R.MAX_NODES]
+    assert any((lev == 4).sum() == 16 and ((lev == 5) & (t["left"] == -1)).sum() == 32 for t, lev in full)
+    assert any(t["left"].size == R.MAX_NODES for t in cases["cap"]["per_user"][0])
+    for n, c in cases.items():
+        if c["max_depth"] == 5:
+            assert max(_levels(t).max() for p in c["per_user"] for t in p) == 5, n
+    # several waves: a split found by a thread of the block's first wave and one by its last
+    for n in ("d65", "d257", "d512"):
+        feats, last = _split_features(cases[n]), 64 * ((cases[n]["D"] - 1) // 64)
+        assert min(feats) < 64 and max(feats) >= last, (n, sorted(feats))
+    # the special values decide splits: a cut among the denormals, one on the colliding column
+    c = cases["denormal"]
+    sub = [t["cond"][i] for p in c["per_user"] for t in p for i in range(t["left"].size)
+           if t["left"][i] != -1 and t["split"][i] in (1, 2)]
+    assert sub and all(abs(v) < F32(1.17549435e-38) for v in sub), sub
+    c = cases["collide"]
+    col = c["X"][c["rows"][:c["row_offsets"][1]], 1]
+    assert 1 in _split_features(c) and not np.array_equal(np.argsort(col, kind="stable"),
+                                                          np.argsort(col.astype(F32), kind="stable"))
+    c = cases["twice"]
+    assert np.unique(c["rows"]).size == c["rows"].size - 4
+    assert cases["overflow"]["status"] == [0, 1, 0] and not cases["overflow"]["per_user"][1]
+    assert sum(n > 0 for n in cases["many"]["counts"]) > 256  # more blocks with work than the device has compute units
 
 
 def test_rejected_configurations():

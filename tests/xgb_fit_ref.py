@@ -51,7 +51,12 @@ def gradients(m, y):
 
 
 def gain(G, H, lam):
-    return G * G / (H + lam)
+    """G^2 / (H + lambda) as an IEEE double division: at lambda = 0 a side whose
+    hessians cancel to 0.0 gives inf (nan from 0 / 0), which need_replace skips."""
+    d = H + lam
+    if d == 0.0:
+        return math.nan if G == 0.0 else math.inf
+    return G * G / d
 
 
 def need_replace(best, loss_chg, f):
@@ -82,6 +87,7 @@ def node_sums(g, h, pos, nid):
 
 
 TIES = {"feature": 0, "scan": 0}  # exact loss_chg ties met so far: between two features / within one feature's scan
+SKIPPED = {"non_finite": 0}       # candidates met so far whose loss_chg was inf or nan
 
 
 def grow_tree(X, order, g, h, max_depth, eta, lam, mcw, log=None):
@@ -114,6 +120,8 @@ def grow_tree(X, order, g, h, max_depth, eta, lam, mcw, log=None):
                     cG, cH = stats[nid][0] - en[0], stats[nid][1] - en[1]
                     if cH >= mcw:
                         loss_chg = F32(gain(cG, cH, lam) + gain(en[0], en[1], lam) - float(stats[nid][3]))
+                        if not math.isfinite(float(loss_chg)):
+                            SKIPPED["non_finite"] += 1
                         if loss_chg == best[nid][0] and loss_chg > F32(0.0):
                             TIES["scan" if best[nid][1] == f else "feature"] += 1
                         if need_replace(best[nid], loss_chg, f):
@@ -266,7 +274,10 @@ def batch(n, D, C, kind="ties", seed=0):
       single   one label only
       lacking  the last class absent from the batch
       mirror   the labels are the pairs' alone (the mirrored counts hold for every class)
-      hand     the hand-worked shape: column 0 counts the rows, the upper half is class 1"""
+      hand     the hand-worked shape: column 0 counts the rows, the upper half is class 1
+      last     the four values sit in the LAST column, column 0 is their upper bit: the cuts 0.5 and
+               2.5 exist in the last column alone, the cut 1.5 in both (an exact tie that column 0
+               wins); most labels are 0, 1, 1, 2 by the value, so the trees want the outer cuts"""
     rng = np.random.default_rng(seed)
     X = rng.normal(size=(n, D))
     q = rng.integers(0, 4, (n + 1) // 2)
@@ -276,7 +287,7 @@ def batch(n, D, C, kind="ties", seed=0):
     if D > 2:
         rule = (np.floor(2.0 * X[:, 1]).astype(np.int64) + (X[:, D // 2] > 0)) % C
         y = y if kind == "mirror" else np.where(rng.random(n) < 0.5, rule, y)
-        X[:, 1:D - 1] = np.round(X[:, 1:D - 1], 1) if kind == "ties" else X[:, 1:D - 1]
+        X[:, 1:D - 1] = np.round(X[:, 1:D - 1], 1) if kind in ("ties", "last") else X[:, 1:D - 1]
     if D > 1:
         X[:, D - 1] = X[:, 0]
     if kind == "const" and D > 2:
@@ -288,6 +299,9 @@ def batch(n, D, C, kind="ties", seed=0):
     if kind == "hand":
         X[:, 0] = np.arange(n)
         y = (2 * np.arange(n) >= n).astype(np.int64)
+    if kind == "last":
+        y = np.where(rng.random(n) < 0.8, np.array([0, 1, 1, 2])[X[:, D - 1].astype(np.int64)] % C, y)
+        X[:, 0] = np.floor(X[:, D - 1] / 2.0)
     return X, y.astype(np.int64)
 
 
@@ -339,23 +353,103 @@ CASES = {
                     f64=True),
     "uniform": dict(D=5, C=4, rounds=1, max_depth=3, rows=(130, 6, 0), kinds=("mirror", "ties", "ties"), base=0, f64=False),
 }
+# The edge cases of tests/test_gpu_xgb_fit_edges.py: the kernel's own limits (the 4096-row cap, the rows taken 8
+# and blockDim at a time, 63-node trees, the one-wave / two-wave / above-64-KiB-LDS feature counts, 8 groups, the
+# three parameters, more users than compute units, a row stride, special values).  As CASES, with EDGE_DEFAULTS and:
+#   seeds    each user's batch seed (100 + u when absent)
+#   eta, lam, mcw   the fit's parameters
+#   pad      padding columns behind X's D (the device test fills them with NaN)
+#   values   special feature values, see ``special_values``
+#   flagged  users whose batch the fit must flag 1 and leave alone
+#   base     "steep": ``steep_model``, start margins 80 apart -- rows whose hessian is the 1e-16 floor next to rows
+#            of 0.5, so that at lambda = 0 and min_child_weight = 0 a side's hessians cancel to 0.0 (loss_chg inf)
+EDGE_DEFAULTS = dict(C=3, rounds=1, base=0, f64=False, eta=0.3, lam=1.0, mcw=1.0, pad=0, values=None, flagged=())
+EDGE_CASES = {
+    "rows8":     dict(D=3, max_depth=3, rows=(7, 8, 9)),
+    "rows64":    dict(D=3, max_depth=3, rows=(63, 64, 65)),
+    "rows512":   dict(D=3, max_depth=3, rows=(255, 256, 257, 0, 513)),
+    "cap":       dict(D=4, max_depth=5, rows=(4096, 4095, 1)),
+    "full":      dict(D=4, max_depth=5, rounds=2, rows=(1024, 2048), seeds=(8, 0)),
+    "d64":       dict(D=64, max_depth=3, rows=(65, 7), kinds=("last", "ties")),
+    "d65":       dict(D=65, max_depth=3, rows=(65, 7), kinds=("last", "ties")),
+    "d257":      dict(D=257, max_depth=3, rows=(40, 3), kinds=("last", "ties")),
+    "d512":      dict(D=512, max_depth=5, rows=(16, 130), kinds=("ties", "last"), seeds=(100, 1)),
+    "d512cap":   dict(D=512, max_depth=1, rows=(4096,)),
+    "groups8":   dict(D=5, C=8, max_depth=5, rounds=2, rows=(130, 9)),
+    "params_a":  dict(D=5, max_depth=5, rounds=2, rows=(257,), eta=1.0, lam=3.5, mcw=2.5),
+    "params_b":  dict(D=5, max_depth=5, rows=(257,), eta=0.3, lam=0.0, mcw=0.0),
+    "params_c":  dict(D=5, max_depth=5, rows=(257,), eta=0.05, lam=0.0, mcw=1.0),
+    "many":      dict(D=3, max_depth=2, rows=tuple(u % 13 for u in range(300))),
+    "pad32":     dict(D=5, max_depth=3, rows=(65, 9), pad=3),
+    "pad64":     dict(D=5, max_depth=3, rows=(65, 9), pad=3, f64=True),
+    "denormal":  dict(D=4, max_depth=3, rows=(64, 9), values="denormal"),
+    "collide":   dict(D=4, max_depth=3, rows=(65, 9), values="collide", f64=True),
+    "twice":     dict(D=4, max_depth=3, rows=(65, 9), values="twice"),
+    "overflow":  dict(D=4, max_depth=3, rows=(65, 9, 16), values="overflow", f64=True, flagged=(1,)),
+    "steep":     dict(D=4, max_depth=3, rows=(65, 9), lam=0.0, mcw=0.0, base="steep"),
+}
+PARAM_CASES = ("params_a", "params_b", "params_c")
 _CACHE = {}
+
+
+def special_values(kind, Xu, yu, C, rng):
+    """The batch (Xu, yu) with the special values of ``kind`` written into it; returns the labels.
+      denormal  column 1 drawn from signed zeros, denormals and the least normal float, column 2 half of it
+                (in float32), most labels following column 1's sign
+      collide   column 1: float32 values moved by a few parts in 1e10, so distinct doubles cast to equal
+                floats and the stable order (not the doubles' order) decides them
+      overflow  one entry of 1e39: a finite double, infinite as a float
+    (``twice`` is a matter of the row list, see ``case``.)"""
+    n = Xu.shape[0]
+    if kind == "denormal":
+        vals = np.array([0.0, -0.0, 1e-40, -1e-40, 1.4e-45, 3e-39, 1.17549435e-38, -1.17549435e-38])
+        col = vals[rng.integers(0, vals.size, n)]
+        Xu[:, 1] = col
+        Xu[:, 2] = (col.astype(F32) * F32(0.5)).astype(np.float64)
+        follow = np.where(col > 0, 1, np.where(col < 0, 0, 2)) % C
+        return np.where(rng.random(n) < 0.7, follow, yu)
+    if kind == "collide":
+        col = Xu[:, 1].astype(F32).astype(np.float64)
+        Xu[:, 1] = col * (1.0 + 1e-10 * rng.integers(-3, 4, n))
+        assert np.array_equal(Xu[:, 1].astype(F32), col.astype(F32)) and (Xu[:, 1] != col).any()
+    if kind == "overflow":
+        Xu[min(3, n - 1), 2] = 1e39
+    return yu
+
+
+def steep_model(C, D):
+    """A base of one tree per group: group 0's cuts feature 1 at 0 into leaves of +40 and -40, the others are one
+    leaf of 0.  A row left of the cut has p = (1, e^-40, ...) as floats, one right of it (e^-40, 1 / (C - 1), ...)."""
+    from ce_amd.xgb import synthetic_model
+
+    cut = {"left": np.array([1, -1, -1], np.int32), "right": np.array([2, -1, -1], np.int32),
+           "split": np.array([1, 0, 0], np.int32), "cond": np.array([0.0, 40.0, -40.0], F32),
+           "default_left": np.array([1, 0, 0], np.uint8)}
+    leaf = {"left": np.array([-1], np.int32), "right": np.array([-1], np.int32), "split": np.array([0], np.int32),
+            "cond": np.array([0.0], F32), "default_left": np.array([0], np.uint8)}
+    flat = synthetic_model(n_rounds=1, num_class=C, max_depth=0, num_feature=D, seed=11)
+    return rounds_model(flat, [cut] + [leaf] * (C - 1), list(range(C)))
 
 
 def case(name):
     """The inputs of a parity case, and what the restatement grows from them
     (computed once).  A dict: base (JSON), X [F, D] (rows no user owns
     included), rows / labels / row_offsets (every user's rows in a shuffled
-    order, stacked), per_user (grown trees), info, margins (final, stacked),
-    forests (each user's XgbForest after the fit)."""
+    order, stacked), per_user (grown trees), info, margins (final, stacked; a
+    flagged user's stay 0), forests (each user's XgbForest after the fit),
+    status (the flags the fit must return)."""
     if name in _CACHE:
         return _CACHE[name]
     from ce_amd.xgb import XgbForest, synthetic_model
 
-    c = dict(CASES[name])
+    c = dict(CASES[name]) if name in CASES else dict(EDGE_DEFAULTS, **EDGE_CASES[name])
     D, C, U = c["D"], c["C"], len(c["rows"])
+    kinds, seeds = c.get("kinds", ("ties",) * U), c.get("seeds", tuple(100 + u for u in range(U)))
+    kw = {k: c[k] for k in ("eta", "lam", "mcw") if k in c}
     rng = np.random.default_rng(sum(map(ord, name)))
-    if c["base"]:
+    if c["base"] == "steep":
+        base = steep_model(C, D)
+    elif c["base"]:
         base = synthetic_model(n_rounds=c["base"], num_class=C, max_depth=3, num_feature=D, seed=11)
     else:
         base = synthetic_model(n_rounds=1, num_class=C, max_depth=0, num_feature=D, seed=11)
@@ -366,22 +460,30 @@ def case(name):
     rows, labels, off, at = [], [], [0], 0
     per_user, margins, forests = [], [], []
     for u, n in enumerate(c["rows"]):
-        r = perm[at:at + n]
+        r = perm[at:at + n].copy()
         at += n
-        Xu, yu = batch(n, D, C, c["kinds"][u], seed=100 + u)
+        Xu, yu = batch(n, D, C, kinds[u], seed=seeds[u])
+        if c.get("values") and (c["values"] != "overflow" or u in c["flagged"]):
+            yu = special_values(c["values"], Xu, yu, C, rng)
         X[r] = Xu
+        if c.get("values") == "twice" and n > 5:  # the batch lists two rows of X twice, under their own labels
+            r[5], r[n - 1] = r[2], r[0]
         if not c["f64"]:
             X = X.astype(F32).astype(np.float64)
         rows.append(r)
         labels.append(yu)
         off.append(off[-1] + n)
-        after, m = fit_forest(forest, X[r], yu, c["rounds"], c["max_depth"])
+        if u in c.get("flagged", ()):  # not run: no tree, and its margins stay as they were allocated
+            after, m = forest, np.zeros((n, C), F32)
+        else:
+            after, m = fit_forest(forest, X[r], yu, c["rounds"], c["max_depth"], **kw)
         per_user.append(after.trees[len(forest.trees):])
         margins.append(m)
         forests.append(after)
     c.update(base=base, forest=forest, X=X, U=U, counts=tuple(c["rows"]), rows=np.concatenate(rows).astype(np.int64),
              labels=np.concatenate(labels).astype(np.int32), row_offsets=np.asarray(off, np.int64),
-             per_user=per_user, margins=np.concatenate(margins), forests=forests,
+             per_user=per_user, margins=np.concatenate(margins), forests=forests, kw=kw,
+             status=[1 if u in c.get("flagged", ()) else 0 for u in range(U)],
              info=[k for _ in range(c["rounds"]) for k in range(C)])
     _CACHE[name] = c
     return c
