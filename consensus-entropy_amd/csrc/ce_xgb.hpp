@@ -74,16 +74,18 @@ struct XgbArgs {
     int64_t ldo;
 };
 
-// Stage frames [f0, f0 + 64) of X as float32 into LDS, feature-major [D][64]
-// swizzled (kXgbCol): wave w takes rows w, w + W, ..., its lanes consecutive
-// features of a row (coalesced loads; conflict-free writes: bank r ^ lane), 2
-// rows x 8 feature chunks per lane in flight; rows past the end repeat the
-// last frame.  No index division: the round-5 loop's e / D cost ~40 VALU per
-// element -- a third of the kernel's VALU (PMC r06).
+// Stage a tile's 64 frames as float32 into LDS, feature-major [D][64] swizzled
+// (kXgbCol); frame r of the tile is row row_of(r) of X, r wave-uniform in
+// [0, 64) and the row a valid one for every r.  Wave w takes frames w, w + W,
+// ..., its lanes consecutive features of a row (coalesced loads; conflict-free
+// writes: bank r ^ lane), 2 rows x 8 feature chunks per lane in flight.  No
+// index division: the round-5 loop's e / D cost ~40 VALU per element -- a third
+// of the kernel's VALU (PMC r06).  w and lane are the caller's (the users walk
+// passes a lane behind its optimisation barrier).
 // Returns whether this thread staged a NaN (missing value).
-template <int XDT, int KF = kXgbMaxFeat / 64>  // KF: 64-feature chunks per row, >= ceil(D / 64)
-__device__ __forceinline__ bool stage_tile(const void* X, int D, int64_t ld, int64_t f0, int nf, float* xs) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, W = blockDim.x >> 6;
+template <int XDT, int KF, class RowOf>  // KF: 64-feature chunks per row, >= ceil(D / 64)
+__device__ __forceinline__ bool stage_rows(const void* X, int D, int64_t ld, RowOf row_of, float* xs, int w, int lane) {
+    const int W = blockDim.x >> 6;
     bool has_nan = false;
     for (int r0 = w; r0 < kXgbTile; r0 += 2 * W) {  // wave-uniform
         // every load unconditional (clamped row / feature): a load under a branch
@@ -92,7 +94,7 @@ __device__ __forceinline__ bool stage_tile(const void* X, int D, int64_t ld, int
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int r = min(r0 + h * W, kXgbTile - 1);
-            const int64_t row = f0 + min(r, nf - 1);
+            const int64_t row = row_of(r);
 #pragma unroll
             for (int k = 0; k < KF; ++k) {
                 const int f = min(lane + 64 * k, D - 1);
@@ -120,21 +122,22 @@ __device__ __forceinline__ bool stage_tile(const void* X, int D, int64_t ld, int
 }
 
 // f64 frames, two features per lane (16-B loads: half the load instructions of
-// stage_tile for the same bytes): lane l takes features 2 l, 2 l + 1 of each
+// stage_rows for the same bytes): lane l takes features 2 l, 2 l + 1 of each
 // 128-feature chunk; the pair is clamped to start <= D - 2 (D >= 2), so every
 // load stays inside the row and is unconditional.  A/B on one box
 // (profiles/r06_xgb.json): 3.279 -> 3.245 ms at 4M frames (dense), 3.418 ->
 // 3.390 ms (missing values).
-template <int KP>  // KP: 128-feature chunks per row, >= ceil(D / 128)
-__device__ __forceinline__ bool stage_tile_pairs(const double* X, int D, int64_t ld, int64_t f0, int nf, float* xs) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, W = blockDim.x >> 6;
+template <int KP, class RowOf>  // KP: 128-feature chunks per row, >= ceil(D / 128)
+__device__ __forceinline__ bool stage_rows_pairs(const double* X, int D, int64_t ld, RowOf row_of, float* xs, int w,
+                                                 int lane) {
+    const int W = blockDim.x >> 6;
     bool has_nan = false;
     for (int r0 = w; r0 < kXgbTile; r0 += 2 * W) {  // wave-uniform
         double2 v[2][KP];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int r = min(r0 + h * W, kXgbTile - 1);
-            const int64_t row = f0 + min(r, nf - 1);
+            const int64_t row = row_of(r);
 #pragma unroll
             for (int k = 0; k < KP; ++k) {
                 const int fl = min(2 * lane + 128 * k, D - 2);
@@ -166,15 +169,9 @@ __device__ __forceinline__ bool stage_tile_pairs(const double* X, int D, int64_t
     return has_nan;
 }
 
-// The objective's transform of the G margins mg[g * 64 + lane] of frame f0 +
-// lane, written to out (wave 0, one frame per lane).
-template <int ODT>
-__device__ __forceinline__ void transform_store(const float* mg, int G, int C, int64_t f0, int nf, void* out,
-                                                int64_t ldo) {
-    const int lane = threadIdx.x & 63;
-    if (threadIdx.x >= 64 || lane >= nf) return;
-    const int64_t fr = f0 + lane;
-    float p[kXgbMaxGroups];
+// The objective's transform: the float32 probabilities p[0 .. C) of the tile's
+// frame `lane` from its G margins mg[g * 64 + lane].
+__device__ __forceinline__ void xgb_proba(const float* mg, int G, int lane, float (&p)[kXgbMaxGroups]) {
     if (G == 1) {  // binary:logistic -> [1 - p, p]
         const float m = mg[lane];
         const float p1 = 1.0f / (1.0f + glibc_expf(-m));
@@ -191,6 +188,17 @@ __device__ __forceinline__ void transform_store(const float* mg, int G, int C, i
         const float ws = (float)wsum;
         for (int g = 0; g < G; ++g) p[g] /= ws;
     }
+}
+
+// xgb_proba of frame f0 + lane, written to out (wave 0, one frame per lane).
+template <int ODT>
+__device__ __forceinline__ void transform_store(const float* mg, int G, int C, int64_t f0, int nf, void* out,
+                                                int64_t ldo) {
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x >= 64 || lane >= nf) return;
+    const int64_t fr = f0 + lane;
+    float p[kXgbMaxGroups];
+    xgb_proba(mg, G, lane, p);
     for (int c = 0; c < C; ++c) {
         if constexpr (ODT == CE_F64)
             static_cast<double*>(out)[fr * ldo + c] = (double)p[c];

@@ -26,10 +26,12 @@
 // inactive slot of a tile loads the row of the tile's first active slot (a
 // valid row, and no missing value the tile does not hold) and is never stored.
 //
-// Against the one-forest kernels: the staging (stage_tile, stage_tile_pairs),
-// LaneTableForest::walk8 and transform_store are restated here over the tile's
-// rows and tree_ids -- sharing their text changed the code of k_xgb_walk and
-// k_xgb_lanes -- and the tests hold the two to the same bits.
+// Against the one-forest kernels nothing of the arithmetic is stated here a
+// second time: the staging (stage_rows, stage_rows_pairs: ce_xgb.hpp) takes the
+// tile's rows through a functor, the walk (table_walk8: ce_xgb_walk.hpp) the
+// table row of a logical tree through UsersForest::row, and the probabilities
+// are xgb_proba's (ce_xgb.hpp).  This header holds what differs: the geometry,
+// the tile's rows and the finishes.
 #pragma once
 #include <algorithm>
 
@@ -38,7 +40,7 @@
 
 namespace ce {
 
-// Lane-table walk over tree_ids: LaneTableForest's walk with logical tree k at
+// Lane tables read through tree_ids: LaneTableForest with logical tree k at
 // table row ids[k] (a wave-uniform scalar load; the debug build checks < TT).
 struct UsersForest : XgbGeom {
     const uint2* table;     // [TT][64], fx with default_left in bit 31
@@ -56,55 +58,7 @@ struct UsersForest : XgbGeom {
     __device__ __forceinline__ void walk8(const float* xs, int D, int t0, int t1, int lane, int (&li)[8],
                                           float (&v)[8]) const {
         (void)D;
-        const uint2* tb = MISS ? table : table_nd;
-        const uint2* tr[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) tr[j] = tb + row(tree(t0, j, t1));
-        uint2 e[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) e[j] = tr[j][lane];
-        const uint32_t lane4 = 4u * (uint32_t)lane;
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            int h[4];  // the lane's heap index x 4: root 4, children 2 h + 4 b
-#pragma unroll
-            for (int j = 0; j < 4; ++j) h[j] = 4;
-            uint4 q0[4], q1[4];  // entries 0..3 of each tree: wave-uniform, scalar loads
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint4* p = reinterpret_cast<const uint4*>(tr[4 * g + j]);
-                q0[j] = p[0];
-                q1[j] = p[1];
-            }
-            if (depth >= 1) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) h[j] = table_right<MISS>(q0[j].z, q0[j].w, xs, lane4) ? 12 : 8;
-            }
-            if (depth >= 2) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool rt = h[j] == 12;
-                    const uint32_t f = rt ? q1[j].z : q1[j].x, th = rt ? q1[j].w : q1[j].y;
-                    h[j] = 2 * h[j] + (table_right<MISS>(f, th, xs, lane4) ? 4 : 0);
-                }
-            }
-            for (int lev = 2; lev < depth; ++lev) {
-                uint32_t f[4], th[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    f[j] = bperm(h[j], e[4 * g + j].x);
-                    th[j] = bperm(h[j], e[4 * g + j].y);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) h[j] = 2 * h[j] + (table_right<MISS>(f[j], th[j], xs, lane4) ? 4 : 0);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                li[4 * g + j] = (h[j] >> 2) - (NI + 1);
-                CE_DASSERT(li[4 * g + j] >= 0 && li[4 * g + j] <= NI);
-                if constexpr (VALS) v[4 * g + j] = __uint_as_float(bperm(h[j], e[4 * g + j].y));
-            }
-        }
+        table_walk8<MISS, VALS>(*this, MISS ? table : table_nd, xs, t0, t1, lane, li, v);
     }
     __device__ __forceinline__ float value(int t, int li) const {
         CE_DASSERT(li >= 0 && li <= NI);
@@ -125,108 +79,6 @@ __device__ __forceinline__ int64_t readlane64(int64_t v, int l) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), l);
     return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// stage_tile over the tile's rows: frame r of the tile is row rows[lane r] of X
-// (every lane of every wave holds the tile's 64 rows, one per lane).
-template <int XDT, int KF>
-__device__ __forceinline__ bool stage_rows(const void* X, int D, int64_t ld, int64_t rows, float* xs, int w, int lane) {
-    const int W = blockDim.x >> 6;
-    bool has_nan = false;
-    for (int r0 = w; r0 < kXgbTile; r0 += 2 * W) {  // wave-uniform
-        typename std::conditional<XDT == CE_F64, double, float>::type v[2][KF];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int r = min(r0 + h * W, kXgbTile - 1);
-            const int64_t row = readlane64(rows, r);
-#pragma unroll
-            for (int k = 0; k < KF; ++k) {
-                const int f = min(lane + 64 * k, D - 1);
-                if constexpr (XDT == CE_F64)
-                    v[h][k] = static_cast<const double*>(X)[row * ld + f];
-                else
-                    v[h][k] = static_cast<const float*>(X)[row * ld + f];
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int r = r0 + h * W;
-#pragma unroll
-            for (int k = 0; k < KF; ++k) {
-                const int f = lane + 64 * k;
-                if (f < D && r < kXgbTile) {
-                    const float x = (float)v[h][k];
-                    xs[f * kXgbCol + (r ^ lane)] = x;  // (f & 63) == lane
-                    has_nan |= __builtin_isnan(x);
-                }
-            }
-        }
-    }
-    return has_nan;
-}
-
-// stage_tile_pairs over the tile's rows (f64 frames, D >= 2)
-template <int KP>
-__device__ __forceinline__ bool stage_rows_pairs(const double* X, int D, int64_t ld, int64_t rows, float* xs, int w,
-                                                 int lane) {
-    const int W = blockDim.x >> 6;
-    bool has_nan = false;
-    for (int r0 = w; r0 < kXgbTile; r0 += 2 * W) {  // wave-uniform
-        double2 v[2][KP];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int r = min(r0 + h * W, kXgbTile - 1);
-            const int64_t row = readlane64(rows, r);
-#pragma unroll
-            for (int k = 0; k < KP; ++k) {
-                const int fl = min(2 * lane + 128 * k, D - 2);
-                const double* src = X + row * ld + fl;
-                v[h][k] = make_double2(src[0], src[1]);
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int r = r0 + h * W;
-#pragma unroll
-            for (int k = 0; k < KP; ++k) {
-                const int f = 2 * lane + 128 * k, fl = min(f, D - 2);
-                if (r < kXgbTile) {
-                    if (f < D) {  // f > fl only for f = D - 1 (odd D): the pair's second value
-                        const float x = (float)(f == fl ? v[h][k].x : v[h][k].y);
-                        xs[f * kXgbCol + (r ^ (f & 63))] = x;
-                        has_nan |= __builtin_isnan(x);
-                    }
-                    if (f + 1 < D && f == fl) {
-                        const float x = (float)v[h][k].y;
-                        xs[(f + 1) * kXgbCol + (r ^ ((f + 1) & 63))] = x;
-                        has_nan |= __builtin_isnan(x);
-                    }
-                }
-            }
-        }
-    }
-    return has_nan;
-}
-
-// transform_store's arithmetic: the float32 probabilities p[0 .. C) of the
-// tile's frame `lane` from its G margins mg[g * 64 + lane].
-__device__ __forceinline__ void users_proba(const float* mg, int G, int lane, float (&p)[kXgbMaxGroups]) {
-    if (G == 1) {  // binary:logistic -> [1 - p, p]
-        const float m = mg[lane];
-        const float p1 = 1.0f / (1.0f + glibc_expf(-m));
-        p[0] = 1.0f - p1;
-        p[1] = p1;
-    } else {  // multi:softprob -> common::Softmax
-        float mx = mg[lane];
-        for (int g = 1; g < G; ++g) mx = fmaxf(mg[g * 64 + lane], mx);
-        double wsum = 0.0;
-        for (int g = 0; g < G; ++g) {
-            p[g] = glibc_expf(mg[g * 64 + lane] - mx);
-            wsum += p[g];
-        }
-        const float ws = (float)wsum;
-        for (int g = 0; g < G; ++g) p[g] /= ws;
-    }
 }
 
 // dynamic LDS: the one-forest kernels' tile (xs, mg, the missing-value votes:
@@ -286,14 +138,15 @@ __device__ __forceinline__ void xgb_users(const XgbArgs& a, const XgbUsersForest
             // rowl, nanw and mg are free: every wave is past the previous tile's last phase barrier,
             // wave 0 (the only reader after it) past its finish
             if (w == 0) rowl[lane] = act ? row : -1;
+            const auto row_of = [&](int r) { return readlane64(rows, r); };  // every lane holds the row of slot `lane`
             bool has_nan;
             if constexpr (XDT == CE_F64) {
                 if (a.D >= 2)
-                    has_nan = stage_rows_pairs<(KF + 1) / 2>(static_cast<const double*>(a.X), a.D, a.ld, rows, xs, w, lane);
+                    has_nan = stage_rows_pairs<(KF + 1) / 2>(static_cast<const double*>(a.X), a.D, a.ld, row_of, xs, w, lane);
                 else
-                    has_nan = stage_rows<XDT, KF>(a.X, a.D, a.ld, rows, xs, w, lane);
+                    has_nan = stage_rows<XDT, KF>(a.X, a.D, a.ld, row_of, xs, w, lane);
             } else {
-                has_nan = stage_rows<XDT, KF>(a.X, a.D, a.ld, rows, xs, w, lane);
+                has_nan = stage_rows<XDT, KF>(a.X, a.D, a.ld, row_of, xs, w, lane);
             }
             {
                 const bool wn = __ballot(has_nan) != 0;
@@ -313,7 +166,7 @@ __device__ __forceinline__ void xgb_users(const XgbArgs& a, const XgbUsersForest
                         fin.margins(mg, a.G, lane, q0 + lane);
                     } else {
                         float pr[kXgbMaxGroups];
-                        users_proba(mg, a.G, lane, pr);
+                        xgb_proba(mg, a.G, lane, pr);
                         fin.row(pr, a.C, ro);
                     }
                 }

@@ -2,7 +2,8 @@
 // margin chain over any of them and the kernels (ce_xgb.hpp: what is computed,
 // the packed layout, the LDS tile).  Its kernels are instantiated by ce_xgb.hip
 // alone; ce_xgb_users.hpp instantiates the margin chain (split_margins) over a
-// layout of its own, UsersForest, for the kernels of ce_xgb_users.hip.
+// layout of its own, UsersForest, for the kernels of ce_xgb_users.hip, and
+// walks it with this header's table_walk8.
 #pragma once
 #include "ce_xgb.hpp"
 
@@ -232,71 +233,93 @@ struct LaneForest : PackedForest {
 // on-the-fly tables (PMC r06: VALU 72 % busy, 80 VALU per tree and wave).  Two
 // halves [2][T][64]: the second without the default_left bits, read by tiles
 // without a missing value (no mask per node read).
+//
+// The walk is table_walk8, one text for every forest over such tables: F gives
+// the geometry and row(k), the entry offset of logical tree k (LaneTableForest:
+// k itself; UsersForest, ce_xgb_users.hpp: through tree_ids).  The rows are
+// formed first (tr[8]) and both the coalesced loads and the scalar loads read
+// through them: worded so, every kernel of the users form and of the fit is
+// byte for byte what it was while the walk stood there a second time
+// (profiles/xgb_one_text_codeobj.json); k_xgb_lanes' code moved, within its
+// registers, and was timed against the parent's (profiles/xgb_one_text_ab.json).
+//
+// 4 trees at a time (two rounds per batch of 8): 4 independent chains per
+// lane keep every level's 8 bpermutes in flight within the 64-VGPR budget of
+// 8 waves per SIMD (8 chains forced the compiler to serialize the split
+// conditions' bpermutes behind lgkmcnt(0)); the second round's tables are
+// loaded with the first's.
+template <bool MISS, bool VALS, class F>
+__device__ __forceinline__ void table_walk8(const F& f, const uint2* tb, const float* xs, int t0, int t1, int lane,
+                                            int (&li)[8], float (&v)[8]) {
+    const uint2* tr[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tr[j] = tb + f.row(F::tree(t0, j, t1));
+    uint2 e[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) e[j] = tr[j][lane];
+    const uint32_t lane4 = 4u * (uint32_t)lane;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        int h[4];  // the lane's heap index x 4 (a ds_bpermute byte address): root 4, children 2 h + 4 b
+#pragma unroll
+        for (int j = 0; j < 4; ++j) h[j] = 4;
+        // entries 0..3 of each tree (root 1, level-1 pair 2 / 3): 32 wave-uniform
+        // bytes, scalar loads issued together before the first use (one wait)
+        uint4 q0[4], q1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint4* p = reinterpret_cast<const uint4*>(tr[4 * g + j]);
+            q0[j] = p[0];
+            q1[j] = p[1];
+        }
+        if (f.depth >= 1) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[j] = table_right<MISS>(q0[j].z, q0[j].w, xs, lane4) ? 12 : 8;
+        }
+        if (f.depth >= 2) {  // level 1 from the pair {2, 3} and a select
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool rt = h[j] == 12;
+                const uint32_t fx = rt ? q1[j].z : q1[j].x, th = rt ? q1[j].w : q1[j].y;
+                h[j] = 2 * h[j] + (table_right<MISS>(fx, th, xs, lane4) ? 4 : 0);
+            }
+        }
+        for (int lev = 2; lev < f.depth; ++lev) {
+            uint32_t fx[4], th[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                fx[j] = F::bperm(h[j], e[4 * g + j].x);
+                th[j] = F::bperm(h[j], e[4 * g + j].y);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[j] = 2 * h[j] + (table_right<MISS>(fx[j], th[j], xs, lane4) ? 4 : 0);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            li[4 * g + j] = (h[j] >> 2) - (f.NI + 1);
+            CE_DASSERT(li[4 * g + j] >= 0 && li[4 * g + j] <= f.NI);
+            if constexpr (VALS) v[4 * g + j] = __uint_as_float(F::bperm(h[j], e[4 * g + j].y));
+        }
+    }
+}
+
 struct LaneTableForest : XgbGeom {
     const uint2* table;     // [T][64], fx with default_left in bit 31 (tiles holding a missing value)
     const uint2* table_nd;  // [T][64], fx without it (the other tiles: no mask per node read)
 
-    // 4 trees at a time (two rounds per batch of 8): 4 independent chains per
-    // lane keep every level's 8 bpermutes in flight within the 64-VGPR budget of
-    // 8 waves per SIMD (8 chains forced the compiler to serialize the split
-    // conditions' bpermutes behind lgkmcnt(0)); the second round's tables are
-    // loaded with the first's.
+    __device__ __forceinline__ int64_t row(int t) const {
+        CE_DASSERT(t >= 0 && t < goff_end);
+        return (int64_t)t * 64;
+    }
     template <bool MISS, bool VALS>
     __device__ __forceinline__ void walk8(const float* xs, int D, int t0, int t1, int lane, int (&li)[8],
                                           float (&v)[8]) const {
         (void)D;
-        const uint2* tb = MISS ? table : table_nd;
-        uint2 e[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) e[j] = tb[(int64_t)tree(t0, j, t1) * 64 + lane];
-        const uint32_t lane4 = 4u * (uint32_t)lane;
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            int h[4];  // the lane's heap index x 4 (a ds_bpermute byte address): root 4, children 2 h + 4 b
-#pragma unroll
-            for (int j = 0; j < 4; ++j) h[j] = 4;
-            // entries 0..3 of each tree (root 1, level-1 pair 2 / 3): 32 wave-uniform
-            // bytes, scalar loads issued together before the first use (one wait)
-            uint4 q0[4], q1[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint4* p = reinterpret_cast<const uint4*>(tb + (int64_t)tree(t0, 4 * g + j, t1) * 64);
-                q0[j] = p[0];
-                q1[j] = p[1];
-            }
-            if (depth >= 1) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) h[j] = table_right<MISS>(q0[j].z, q0[j].w, xs, lane4) ? 12 : 8;
-            }
-            if (depth >= 2) {  // level 1 from the pair {2, 3} and a select
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool rt = h[j] == 12;
-                    const uint32_t f = rt ? q1[j].z : q1[j].x, th = rt ? q1[j].w : q1[j].y;
-                    h[j] = 2 * h[j] + (table_right<MISS>(f, th, xs, lane4) ? 4 : 0);
-                }
-            }
-            for (int lev = 2; lev < depth; ++lev) {
-                uint32_t f[4], th[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    f[j] = bperm(h[j], e[4 * g + j].x);
-                    th[j] = bperm(h[j], e[4 * g + j].y);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) h[j] = 2 * h[j] + (table_right<MISS>(f[j], th[j], xs, lane4) ? 4 : 0);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                li[4 * g + j] = (h[j] >> 2) - (NI + 1);
-                CE_DASSERT(li[4 * g + j] >= 0 && li[4 * g + j] <= NI);
-                if constexpr (VALS) v[4 * g + j] = __uint_as_float(bperm(h[j], e[4 * g + j].y));
-            }
-        }
+        table_walk8<MISS, VALS>(*this, MISS ? table : table_nd, xs, t0, t1, lane, li, v);
     }
     __device__ __forceinline__ float value(int t, int li) const {
-        CE_DASSERT(t >= 0 && t < goff_end && li >= 0 && li <= NI);
-        return __uint_as_float(table[(int64_t)t * 64 + NI + 1 + li].y);
+        CE_DASSERT(li >= 0 && li <= NI);
+        return __uint_as_float(table[row(t) + NI + 1 + li].y);
     }
 };
 
@@ -382,14 +405,15 @@ __device__ __forceinline__ void xgb_tile(const XgbArgs& a, const L& fl) {
     const int g = w / a.S, s = w - g * a.S;
     const int64_t f0 = (int64_t)blockIdx.x * kXgbTile;
     const int nf = (int)min<int64_t>(kXgbTile, a.F - f0);
+    const auto row_of = [&](int r) { return f0 + min(r, nf - 1); };  // slots past the end repeat the last frame
     bool has_nan;
     if constexpr (XDT == CE_F64 && KF < kXgbMaxFeat / 64) {  // (the lane-table kernel's widths)
         if (a.D >= 2)
-            has_nan = stage_tile_pairs<(KF + 1) / 2>(static_cast<const double*>(a.X), a.D, a.ld, f0, nf, xs);
+            has_nan = stage_rows_pairs<(KF + 1) / 2>(static_cast<const double*>(a.X), a.D, a.ld, row_of, xs, w, lane);
         else
-            has_nan = stage_tile<XDT, KF>(a.X, a.D, a.ld, f0, nf, xs);
+            has_nan = stage_rows<XDT, KF>(a.X, a.D, a.ld, row_of, xs, w, lane);
     } else {
-        has_nan = stage_tile<XDT, KF>(a.X, a.D, a.ld, f0, nf, xs);
+        has_nan = stage_rows<XDT, KF>(a.X, a.D, a.ld, row_of, xs, w, lane);
     }
     // the block's "any NaN" vote through the dynamic LDS (__syncthreads_or keeps
     // a static LDS word, which puts the tile 256 B off address 0: one more VALU

@@ -79,6 +79,28 @@ def test_xgb_bit_exact(ce, name, kw, F, nan):
     assert np.array_equal(bits(got), bits(exp)), (np.argwhere(bits(got) != bits(exp))[:5], name)
 
 
+@pytest.mark.parametrize("nan", [0.03, 0.0], ids=["missing", "dense"])
+@pytest.mark.parametrize("xdt", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("D", [1, 2, 3, 128, 129, 256, 257, 320, 321, 512])
+def test_xgb_lanes_staging_widths(ce, D, xdt, nan):
+    """The lane-table kernel's staging (one text with the users form's) on both
+    sides of every step of its width ladder (64-feature chunks 2 / 4 / 5 / 8
+    at D <= 128 / 256 / 320 / 512) and at the pair loader's D - 2 clamp
+    (D = 2, 3; D = 1 takes the single loads), f64 and f32 frames, one full
+    tile and one ragged one."""
+    F = 64 + 37
+    model = synthetic_model(n_rounds=4, num_class=4, max_depth=3, num_feature=D, seed=100 + D)
+    forest = XgbForest.from_json(model)
+    X = frames(F, D, seed=D, nan=nan, model=model).astype(xdt)
+    if nan:  # a missing value in either tile, the second in the last feature
+        X[5, 0] = X[64 + 5, D - 1] = np.nan
+    exp = O.oracle_xgb_predict_proba(X.astype(np.float64), model)
+    Xd = dev(X)
+    assert forest.device_arrays(Xd.device)[3] <= ce.ops.LANE_TABLE_DEPTH  # so ce_xgb_predict_proba_lanes runs
+    got = ce.ops.xgb_predict_proba(Xd, forest).cpu().numpy()
+    assert np.array_equal(bits(got), bits(exp)), (np.argwhere(bits(got) != bits(exp))[:5], D)
+
+
 def test_xgb_sparse_missing_tiles(ce):
     """A few NaN frames scattered over many tiles: tiles with and without a
     missing value in one launch."""
