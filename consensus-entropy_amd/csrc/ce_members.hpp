@@ -17,7 +17,11 @@
 //     p_k = expit(d_k) = 1 / (1 + exp(-d_k)) (glibc's exp), then p /= sum_k p_k (OvR, K > 1),
 //     or [1 - p, p] for a binary model.  The dot products are BLAS dgemm in the
 //     reference (an unspecified order); here a fixed wave-reduction order --
-//     parity is to a tolerance (tests state it).
+//     parity with sklearn is to a tolerance (tests state it).  After the dot
+//     product the order is sklearn's: sum_k is numpy's prob.sum(axis=1) over a
+//     C-contiguous row (sgd_store: sequential below 8 classes, the 8-accumulator
+//     tree at 8), so from the decision values on the bits are the restatement's
+//     (tests/members_proba_ref.py sgd_proba).
 //
 // Eight lanes per frame, eight frames per wave: lane j of a group owns the
 // features f = 8m + j -- exactly numpy's eight pairwise accumulators (leaves
@@ -469,7 +473,12 @@ __global__ __launch_bounds__(256) void k_sgd_proba8(SgdArgs a) {
     }
 }
 
-// The OvR normalisation (or the binary [1 - p, p]) and the store of lane j's class.
+// The OvR normalisation (or the binary [1 - p, p]) and the store of lane j's
+// class.  The sum is sklearn's prob.sum(axis=1) over a C-contiguous [F, K]
+// array: every row is one numpy pairwise leaf, so fewer than 8 classes are
+// added one after the other onto -0.0 and 8 classes by the 8-accumulator tree
+// ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)), either onto the reduction's 0.0.  (KR:
+// the registers p holds; a kernel with a compile-time K < 8 has no tree branch.)
 template <int KR>
 __device__ __forceinline__ void sgd_store(const SgdArgs& a, double (&p)[KR], int K, int64_t fr, int j) {
     if (K == 1) {
@@ -477,7 +486,13 @@ __device__ __forceinline__ void sgd_store(const SgdArgs& a, double (&p)[KR], int
         p[0] = 1.0 - p[1];
     } else {
         double s = -0.0;
-        for (int c = 0; c < K; ++c) s += p[c];
+        bool tree = false;
+        if constexpr (KR >= 8) tree = K == 8;
+        if (tree) {
+            if constexpr (KR >= 8) s = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+        } else {
+            for (int c = 0; c < K; ++c) s += p[c];
+        }
         s = 0.0 + s;
         for (int c = 0; c < K; ++c) p[c] /= s;
     }

@@ -114,21 +114,28 @@ def ref_group_mean(values, s_id):
     return out, keys
 
 
+def _elementwise(fn, a):
+    """fn (a C loop over n doubles) applied to every element of a; the result
+    has a's memory order, as a numpy ufunc's has (np.exp of an F-ordered array
+    is F-ordered) -- what a later np.sum over it depends on."""
+    a = np.asarray(a, dtype=np.float64)
+    flat = np.ascontiguousarray(a).reshape(-1)
+    vals = np.empty_like(flat)
+    fn(_ptr(flat), flat.size, _ptr(vals))
+    y = np.empty_like(a)  # order 'K': a's layout
+    y[...] = vals.reshape(a.shape)
+    return y
+
+
 def libm_exp(a):
     """np.exp as numpy 1.19.5 evaluates float64 (the C library's exp, element by
     element) -- the installed numpy uses its own SIMD exp."""
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    y = np.empty_like(a)
-    lib().ce_ref_libm_exp(_ptr(a), a.size, _ptr(y))
-    return y
+    return _elementwise(lib().ce_ref_libm_exp, a)
 
 
 def libm_log(a):
     """np.log as numpy 1.19.5 evaluates float64 (the C library's log)."""
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    y = np.empty_like(a)
-    lib().ce_ref_libm_log(_ptr(a), a.size, _ptr(y))
-    return y
+    return _elementwise(lib().ce_ref_libm_log, a)
 
 
 def ref_gnb_predict_proba(X, theta, var, class_prior, exp=None, log=None):
@@ -141,7 +148,15 @@ def ref_gnb_predict_proba(X, theta, var, class_prior, exp=None, log=None):
     exp / log default to the C library's (libm_exp / libm_log: numpy 1.19.5
     calls them for float64; the installed numpy's SIMD exp / log differ by an
     ulp here and there).  The installed scipy >= 1.14 rewrote logsumexp; tests
-    pin this restatement to the installed sklearn within a stated tolerance."""
+    pin this restatement to the installed sklearn within a stated tolerance.
+
+    The order of the class sum: ``jll`` is np.array(jll).T, an F-ordered
+    [F, C] array, and exp(jll - a_max) keeps that layout (libm_exp returns its
+    argument's memory order, as np.exp does).  np.sum(..., axis=1) over an
+    F-ordered array adds whole columns, class after class.  Over a C-ordered
+    copy each row would be one pairwise leaf instead, which for C = 8 is the
+    8-accumulator tree ((e0+e1)+(e2+e3))+((e4+e5)+(e6+e7)) -- other bits on
+    near-tied classes.  Below 8 classes both orders are the sequential one."""
     exp = libm_exp if exp is None else exp
     log = libm_log if log is None else log
     X = np.asarray(X, np.float64)

@@ -3,7 +3,7 @@ ce_sgd_score_users, ce_f1_weighted_users; ops.*_score_users,
 ops.f1_weighted_users, EvalSet, Device*.evaluate, mean_f1).
 
 Scores: the returned jll / decision values give, through the restated
-logsumexp / expit (the C library's exp and log, the kernels' order), the bits of
+logsumexp / expit (the C library's exp and log, numpy's order), the bits of
 ops.*_predict_proba_users on the same geometry -- kernels that are pinned
 already; the GaussianNB scores are also gnb_jll's bits.  Labels: sklearn's rule
 over the returned scores on every counted row, the prefill (-1, NaN) on every
@@ -18,6 +18,7 @@ from conftest import golden
 from gnb_fit_ref import gnb_partial_fit, same_bits
 from members_eval_ref import (confusion, f1_weighted, gnb_jll, libm_exp, libm_log, predict_labels, prf,
                               sgd_decision)
+from members_proba_ref import sgd_proba_from_decision
 from members_users_ref import excl_words, row_owners
 from sgd_fit_ref import sgd_partial_fit
 
@@ -95,10 +96,12 @@ def labels_for(rng, F, C):
 
 
 def proba_from_scores(kind, s, C):
-    """The predict_proba kernels' tail over their own scores, in their order:
-    GaussianNB scipy's logsumexp (the running max, a non-finite max -> 0, the
-    exps added one after the other onto -0.0), SGD expit and the one-vs-rest
-    normalisation ([1 - p, p] for a binary model)."""
+    """sklearn's predict_proba tail over the kernels' scores: GaussianNB scipy's
+    logsumexp (the running max, a non-finite max -> 0, the exps added one after
+    the other onto -0.0: numpy's order over the F-ordered jll), SGD expit and
+    sklearn's own ``p / p.sum(axis=1)`` over a C-contiguous array (numpy's
+    order: 8 classes take the 8-accumulator tree; members_proba_ref), or
+    [1 - p, p] for a binary model."""
     with np.errstate(all="ignore"):
         if kind == "gnb":
             mx = s[:, 0].copy()
@@ -110,13 +113,7 @@ def proba_from_scores(kind, s, C):
                 acc = acc + libm_exp(s[:, c] - mx)
             lse = libm_log(0.0 + acc) + mx
             return libm_exp(s - lse[:, None])
-        p = 1.0 / (1.0 + libm_exp(-s))
-        if s.shape[1] == 1:
-            return np.concatenate([1.0 - p, p], 1)
-        acc = np.full(len(s), -0.0)
-        for c in range(C):
-            acc = acc + p[:, c]
-        return p / (0.0 + acc)[:, None]
+        return sgd_proba_from_decision(s)
 
 
 def score(ce, kind, Xd, models, geom, yd, excl=None):

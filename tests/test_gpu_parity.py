@@ -1209,8 +1209,12 @@ def test_lds_dma_stream_instantiations(ce, dt, C, M):
 
 def test_gnb_widest_shape(ce):
     """GaussianNB at the ABI's limits (C = 8 classes, D = 512 features: 96 KB of
-    theta / var / 1/var in LDS) against the restatement, with variances spread
-    over 12 decades (the reciprocal-corrected division)."""
+    theta / var / 1/var in LDS) against the restatement in all 64 bits, with
+    variances spread over 12 decades (the reciprocal-corrected division).  The
+    probabilities of this data are one-hot, so the joint log-likelihood itself
+    (the scores of ce_gnb_score_users for one user owning every row) is held to
+    members_eval_ref.gnb_jll as well: every term's quotient is in those bits."""
+    from members_eval_ref import gnb_jll
     from oracle.ce_oracle import ref_gnb_predict_proba
 
     rng = np.random.default_rng(512)
@@ -1220,7 +1224,14 @@ def test_gnb_widest_shape(ce):
     prior = rng.dirichlet(np.ones(C))
     X = theta[rng.integers(0, C, 3000)] + rng.normal(0, 1, (3000, D)) * np.sqrt(var[0])
     got = ce.ops.gnb_predict_proba(dev(X), theta, var, prior).cpu().numpy()
-    np.testing.assert_allclose(got, ref_gnb_predict_proba(X, theta, var, prior), rtol=1e-10, atol=1e-300)
+    want = ref_gnb_predict_proba(X, theta, var, prior)
+    assert not np.isnan(want).any()
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64))
+    F = len(X)
+    _, _, jll = ce.ops.gnb_score_users(dev(X), dev(theta[None]), dev(var[None]), dev(prior[None]),
+                                       dev(np.array([0, 1], np.int64)), dev(np.array([0, F], np.int64)),
+                                       dev(np.zeros(F, np.int32)), return_scores=True)
+    assert np.array_equal(jll.cpu().numpy().view(np.uint64), gnb_jll(X, theta, var, prior).view(np.uint64))
 
 
 @pytest.mark.parametrize("C,dt,N,chunk", [(4, "f32", 300_000, 50_000), (1000, "bf16", 6_000, 1_000),
