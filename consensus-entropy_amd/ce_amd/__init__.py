@@ -12,8 +12,9 @@ from .select import (MODES, ConsensusEntropySelector, committee_from_frames, sel
 from .session import SelectionSession  # noqa: F401,E402
 from .batched_session import BatchedSelectionSession  # noqa: F401,E402
 from .members import DeviceGaussianNB, DeviceSGDClassifier, DeviceXGBClassifier, EvalSet, mean_f1  # noqa: F401,E402
+from .cnn import DeviceShortChunkCNN  # noqa: F401,E402
 
-__all__ = ["SelectionSession", "BatchedSelectionSession", "DeviceGaussianNB", "DeviceSGDClassifier", "DeviceXGBClassifier", "EvalSet", "mean_f1", "select_queries", "ConsensusEntropySelector", "stack_committee", "committee_from_frames",
+__all__ = ["SelectionSession", "BatchedSelectionSession", "DeviceGaussianNB", "DeviceSGDClassifier", "DeviceXGBClassifier", "DeviceShortChunkCNN", "EvalSet", "mean_f1", "select_queries", "ConsensusEntropySelector", "stack_committee", "committee_from_frames",
            "select_from_frames", "song_groups",
            "MODES", "CE_MAX_Q", "CEError", "load", "ops", "dist", "torch_ops"]
 

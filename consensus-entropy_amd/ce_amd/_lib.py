@@ -107,6 +107,11 @@ SIGNATURES = {
     "ce_select_batched_mix": (_int, [_vp, _int, _i64, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i32,
                                      _vp, _vp, _i32, _vp, _sz, _vp, _vp, _vp]),
     "ce_mark_selected_batched": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ce_cnn_weights_floats": (_sz, [_i32]),
+    "ce_cnn_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "ce_cnn_logmel": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "ce_cnn_forward_users": (_int, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _i64,
+                                    _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -793,6 +793,66 @@ int ce_mark_selected_batched(const int64_t *idx, int32_t U, int32_t q, const int
                              uint32_t *excl, const int64_t *offsets_h, uint32_t *excl_h,
                              const int64_t *m2h, const int64_t *h2m, ce_stream_t stream);
 
+/*
+ * The short-chunk CNN member, inference (the 'short_cnn' member of
+ * amg_test.py:430 / :462: predict_cnn, :173-201, over short_cnn.py:278-349 in
+ * eval mode), f32 throughout as the reference runs it:
+ *   waveform [L] -> power spectrogram (n_fft = window = 512, hop 256, periodic
+ *   Hann, centred with reflect padding: T = L / 256 + 1 frames, 257 bins)
+ *   -> filter bank fb [257, 128] -> 10 log10(max(x, 1e-10))          (ce_cnn_logmel)
+ *   -> spec_bn -> 7 x (conv 3x3, pad 1, bias -> BatchNorm -> ReLU -> max-pool
+ *   2x2, floor), channels 1 -> nc, nc, 2nc, 2nc, 2nc, 2nc, 4nc -> max over the
+ *   width left -> dense1 -> BatchNorm1d -> ReLU -> dense2 -> sigmoid: [4] per
+ *   excerpt, un-normalised                                    (ce_cnn_forward_users)
+ * BatchNorm uses the running statistics; the caller folds them (and the conv /
+ * dense1 bias) into a per-channel scale and shift, in double, so that a
+ * normalised value is fma(scale, sum, shift).
+ *
+ * ce_cnn_logmel: wave [S, L] f32, row pitch ld_wave >= L (512 <= L < 8 * 65535 * 256) -> mel
+ * [S, 128, T] f32 (dB).  basis [2, 512, 257] f32: plane 0 w[n] cos(2 pi f n /
+ * 512), plane 1 w[n] sin(2 pi f n / 512), w the periodic Hann window -- the DFT
+ * is a product with it, not an FFT.  fb [257, 128] f32 (the state dict's
+ * spec.mel_scale.fb).  One launch.
+ *
+ * Weights: one packed f32 record per model, ce_cnn_weights_floats(nc) floats,
+ * the records stacked [Uw, floats] (256-B aligned).  In order, every part a
+ * multiple of 16 floats:
+ *   spec [16]                scale, shift of spec_bn, zeros
+ *   per block i = 1 .. 7     w [9 Cin, Cout] (row (ky 3 + kx) Cin + ci), scale [Cout], shift [Cout]
+ *   W1 [4nc, 4nc]            dense1.weight TRANSPOSED (input-major)
+ *   s1 [4nc], t1 [4nc]       BatchNorm1d over dense1 (its bias folded into t1)
+ *   W2 [4, 4nc]              dense2.weight
+ *   b2 [16]                  dense2.bias, zeros
+ *
+ * ce_cnn_forward_users: mel [n, 128, T] holds the excerpts s_base .. s_base +
+ * n - 1 of the stacked pool (a batch: n <= 65535); item_offsets [U + 1]
+ * (DEVICE), excl_or_null (a bitmap, ce_excl_words), y_or_null and out are
+ * indexed by the pool position s.  Excerpt s belongs to the user u with
+ * item_offsets[u] <= s < item_offsets[u+1] and runs through record u (Uw == U)
+ * or record 0 (Uw == 1: one shared model).  An excerpt that is excluded or that
+ * no user owns is neither computed nor written.  out [*, 4] f32, row pitch
+ * ld_out >= 4.  y / cm (both or neither): y [*] int32 the class of excerpt s,
+ * cm [U, 4, 4] int64; the predicted class is np.argmax of the four outputs (the
+ * first maximum; a NaN wins at its first occurrence) and cm[u, y, pred] is
+ * bumped with an integer atomic (a label outside [0, 4) is not counted).  cm is
+ * NOT zero-filled here: a pool is walked in batches that add to one cm.
+ * ws: ce_cnn_workspace_bytes(n, T, nc) bytes, two ping-pong activation buffers
+ * (not zero-filled, no header).  Every output is one ordered f32 fma chain (no
+ * split-K, no float atomic): its bits depend on neither n, s_base, U nor Uw.
+ * CE_EINVAL: n_mels != 128, T < 128, nc not a positive multiple of 16 (<= 1024),
+ * Uw neither 1 nor U, bad shapes, a null pointer; CE_EWORKSPACE: a short ws.
+ * All checked before any device call.  8 launches, nothing read back.
+ */
+size_t ce_cnn_weights_floats(int32_t nc);
+size_t ce_cnn_workspace_bytes(int64_t batch, int32_t T, int32_t nc);
+int ce_cnn_logmel(const float *wave, int64_t S, int64_t L, int64_t ld_wave, const float *basis,
+                  const float *fb, float *mel, ce_stream_t stream);
+int ce_cnn_forward_users(const float *mel, int64_t n, int32_t n_mels, int32_t T, const float *weights,
+                         int32_t nc, int32_t Uw, const int64_t *item_offsets, int32_t U,
+                         int64_t s_base, const uint32_t *excl_or_null, const int32_t *y_or_null,
+                         int64_t *cm_or_null, float *out, int64_t ld_out, void *ws, size_t ws_bytes,
+                         ce_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
