@@ -112,6 +112,7 @@ SIGNATURES = {
     "ce_cnn_logmel": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "ce_cnn_forward_users": (_int, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _i64,
                                     _vp, _sz, _vp]),
+    "ce_cnn_activations": (_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

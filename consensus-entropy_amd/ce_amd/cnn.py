@@ -231,6 +231,26 @@ class DeviceShortChunkCNN:
             self._forward(m, w, self._one, 1, b, None, None, None, out)
         return out
 
+    def activations(self, mel, block, u=0):
+        """What block ``block`` (1 .. 7) of model u writes for the log-mel
+        ``mel`` [S, 128, T]: [S, 128 >> block, T >> block, C] f32,
+        channel-innermost, after BatchNorm, ReLU and the pool, by the forward's
+        own launches (ce_cnn_activations).  For tests and diagnosis."""
+        self._check_mel(mel)
+        u, block = int(u), int(block)
+        if not 0 <= u < self.U:
+            raise ValueError(f"user {u} outside [0, {self.U})")
+        if not 1 <= block <= N_BLOCKS:
+            raise ValueError(f"block {block} outside 1 .. {N_BLOCKS}")
+        w = self.weights[u if self.Uw > 1 else 0].unsqueeze(0)
+        n, H, T = mel.shape
+        act = torch.empty((n, N_MELS >> block, max(T, N_MELS) >> block, _CH[block] * self.nc), dtype=torch.float32,
+                          device=mel.device)
+        ws = self._workspace(max(n, 1), max(T, N_MELS), mel.device)
+        call("ce_cnn_activations", _p(mel), n, H, T, _p(w), self.nc, _p(self._one), block, _p(act), _p(ws), ws.numel(),
+             _stream(mel.device))
+        return act
+
     def _users(self, wave, item_offsets, U, excl, y, cm, out, batch):
         self._check_wave(wave)
         S = wave.shape[0]

@@ -104,8 +104,10 @@ __device__ __forceinline__ const float* cnn_model(const CnnGeom& g, int64_t i, i
     return g.weights + (int64_t)lo * g.wstride;
 }
 
-// ReLU and the pool's maximum as torch computes them: a NaN goes through.
+// ReLU, the pool's maximum and the front end's clamp as torch computes them
+// (relu, max_pool2d, clamp(min=)): a NaN goes through.  fmaxf would drop it.
 __device__ __forceinline__ float cnn_relu(float v) { return v < 0.0f ? 0.0f : v; }
+__device__ __forceinline__ float cnn_clamp_min(float v, float lo) { return v < lo ? lo : v; }
 __device__ __forceinline__ float cnn_max(float a, float b) { return (b > a || b != b) ? b : a; }
 
 // ---------------------------------------------------------------- front end
@@ -116,7 +118,8 @@ constexpr int kMelBlk = 32;                                          // terms pe
 // wave [S, L] (row pitch ld), basis [2, 512, 257] (cos plane, sin plane; the
 // window multiplied in), fb [257, 128]; mel [S, 128, T], T = L / 256 + 1.
 // Sums: a bin's 512 terms in 16 partial chains of 32 added in order onto the
-// total; a mel band's 257 terms in one chain.
+// total; a mel band's 257 terms in one chain.  A NaN sample makes every
+// band of the frames that cover it NaN (clamp(min=) keeps a NaN).
 __global__ __launch_bounds__(256) void k_cnn_logmel(const float* __restrict__ wave, int64_t L, int64_t ld,
                                                     const float* __restrict__ basis, const float* __restrict__ fb,
                                                     float* __restrict__ mel, int T) {
@@ -180,7 +183,7 @@ __global__ __launch_bounds__(256) void k_cnn_logmel(const float* __restrict__ wa
 #pragma unroll
     for (int j = 0; j < kMelFrames / 2; ++j) {
         const int t = t0 + jh * (kMelFrames / 2) + j;
-        if (t < T) mel[(s * kCnnMels + m) * T + t] = 10.0f * log10f(fmaxf(acc[j], 1e-10f));
+        if (t < T) mel[(s * kCnnMels + m) * T + t] = 10.0f * log10f(cnn_clamp_min(acc[j], 1e-10f));
     }
 }
 

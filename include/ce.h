@@ -812,7 +812,11 @@ int ce_mark_selected_batched(const int64_t *idx, int32_t U, int32_t q, const int
  * [S, 128, T] f32 (dB).  basis [2, 512, 257] f32: plane 0 w[n] cos(2 pi f n /
  * 512), plane 1 w[n] sin(2 pi f n / 512), w the periodic Hann window -- the DFT
  * is a product with it, not an FFT.  fb [257, 128] f32 (the state dict's
- * spec.mel_scale.fb).  One launch.
+ * spec.mel_scale.fb).  The max is torch.clamp(min = 1e-10): a band without
+ * power (an empty band of the bank, digital silence) is -100 dB, and a NaN
+ * stays a NaN -- every band of the frames that cover a NaN sample is NaN, and
+ * the network carries it to that excerpt's four outputs (ReLU, the pools and
+ * the global max pass a NaN on as torch's do).  One launch.
  *
  * Weights: one packed f32 record per model, ce_cnn_weights_floats(nc) floats,
  * the records stacked [Uw, floats] (256-B aligned).  In order, every part a
@@ -842,6 +846,16 @@ int ce_mark_selected_batched(const int64_t *idx, int32_t U, int32_t q, const int
  * CE_EINVAL: n_mels != 128, T < 128, nc not a positive multiple of 16 (<= 1024),
  * Uw neither 1 nor U, bad shapes, a null pointer; CE_EWORKSPACE: a short ws.
  * All checked before any device call.  8 launches, nothing read back.
+ *
+ * ce_cnn_activations: what block `block` (1 .. 7) of one model writes, for
+ * tests and diagnosis: the forward's own launch sequence (the same kernels,
+ * grids and ping-pong order) over blocks 1 .. block, then a device-to-device
+ * copy on the stream of that block's output into act [n, 128 >> block,
+ * T >> block, C] f32, channel-innermost, C = nc, nc, 2nc, 2nc, 2nc, 2nc, 4nc
+ * (after BatchNorm, ReLU and the pool).  weights: ONE record; no exclusion;
+ * item_offsets [2] (DEVICE) = {0, any value >= n}, the one owner's range as the
+ * forward takes it.  mel, n, n_mels, T, nc, ws as above, and the same errors;
+ * CE_EINVAL also for a block outside 1 .. 7.  block launches and one copy.
  */
 size_t ce_cnn_weights_floats(int32_t nc);
 size_t ce_cnn_workspace_bytes(int64_t batch, int32_t T, int32_t nc);
@@ -852,6 +866,9 @@ int ce_cnn_forward_users(const float *mel, int64_t n, int32_t n_mels, int32_t T,
                          int64_t s_base, const uint32_t *excl_or_null, const int32_t *y_or_null,
                          int64_t *cm_or_null, float *out, int64_t ld_out, void *ws, size_t ws_bytes,
                          ce_stream_t stream);
+int ce_cnn_activations(const float *mel, int64_t n, int32_t n_mels, int32_t T, const float *weights,
+                       int32_t nc, const int64_t *item_offsets, int32_t block, float *act, void *ws,
+                       size_t ws_bytes, ce_stream_t stream);
 
 #ifdef __cplusplus
 }

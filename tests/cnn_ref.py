@@ -10,7 +10,8 @@ in float64 and in float32 on the CPU.
                            the 1e-10 clamp)
   logmel(wave, fb)         the front end from an explicit windowed DFT product
   logmel_stft(wave, fb)    the same through torch.stft
-  body(mel, state)         spec_bn, the seven blocks, the head: [S, 4]
+  activations(mel, state)  spec_bn and the seven blocks: every block's output
+  body(mel, state)         the blocks and the head: [S, 4]
   forward(wave, state)     both
   ratio(dev, f64, f32)     what the tests bound: max |dev - f64| / e32, e32 = max |f32 - f64|
 
@@ -116,17 +117,31 @@ def _bn(x, s, prefix):
                         s[f"{prefix}.bias"], training=False, eps=EPS)
 
 
-def body(mel, state):
-    """mel [S, 128, T] -> [S, 4], in mel's dtype."""
+def activations(mel, state):
+    """mel [S, 128, T] -> what each of the seven blocks writes (after the pool):
+    a list of [S, C_b, 128 >> b, T >> b], in mel's dtype."""
     s = cast(state, mel.dtype)
     x = _bn(mel[:, None], s, "spec_bn")
+    acts = []
     for i in range(1, 8):
         x = F.conv2d(x, s[f"layer{i}.conv.weight"], s[f"layer{i}.conv.bias"], stride=1, padding=1)
         x = F.max_pool2d(F.relu(_bn(x, s, f"layer{i}.bn")), 2)
-    assert x.shape[2] == 1
-    x = x[:, :, 0, :].amax(dim=2)
+        acts.append(x)
+    return acts
+
+
+def logits(feat, state):
+    """The last block's output [S, 4nc, 1, Wf] -> dense2's outputs [S, 4], before the sigmoid."""
+    s = cast(state, feat.dtype)
+    assert feat.shape[2] == 1
+    x = feat[:, :, 0, :].amax(dim=2)
     x = F.relu(_bn(F.linear(x, s["dense1.weight"], s["dense1.bias"]), s, "bn"))
-    return torch.sigmoid(F.linear(x, s["dense2.weight"], s["dense2.bias"]))
+    return F.linear(x, s["dense2.weight"], s["dense2.bias"])
+
+
+def body(mel, state):
+    """mel [S, 128, T] -> [S, 4], in mel's dtype."""
+    return torch.sigmoid(logits(activations(mel, state)[-1], state))
 
 
 def forward(wave, state):
@@ -149,7 +164,8 @@ def ratio(dev, f64, f32):
 
 
 # ---- the cases the GPU tests and tools/cnn_member_probe.py share (computed once per process)
-BODY_CASES = [(16, 3, 128), (16, 3, 231), (16, 3, 255), (16, 3, 300), (128, 2, 231)]  # (nc, S, T)
+# (nc, S, T); nc = 48 is the one with partial Cout tiles in every k_cnn_conv instantiation (48, 96, 192)
+BODY_CASES = [(16, 3, 128), (16, 3, 231), (16, 3, 255), (16, 3, 300), (128, 2, 231), (48, 2, 150)]
 FRONT_CASES = [32768, 59049]  # L, with S = 3
 E2E_CASE = (16, 3, 59049)  # (nc, S, L)
 FLOOR_P = 2.0 ** -22  # about four f32 ulps of a probability

@@ -10,6 +10,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import cnn_exact as X  # noqa: E402
 import cnn_ref as R  # noqa: E402
 
 
@@ -177,6 +178,79 @@ def test_argument_errors_without_gpu():
     too_long = 8 * 65535 * 256  # T = 8 * 65535 + 1 frames: one frame tile more than the grid holds
     assert lib.ce_cnn_logmel(p, 2, too_long, too_long, p, p, p, None) == _lib.CE_EINVAL
     assert b"L=" in lib.ce_last_error()
+
+
+def test_activations_argument_errors_without_gpu():
+    from ce_amd import _lib
+
+    lib = _lib.load()
+    p = ctypes.c_void_p(256)
+    nc, T, n = 16, 231, 2
+    ws = lib.ce_cnn_workspace_bytes(n, T, nc)
+
+    def act(n=n, n_mels=128, T=T, nc=nc, block=3, ws_bytes=ws, mel=p, out=p):
+        return lib.ce_cnn_activations(mel, n, n_mels, T, p, nc, p, block, out, p, ws_bytes, None)
+
+    for bad in (0, 8, -1):
+        assert act(block=bad) == _lib.CE_EINVAL and f"block={bad}".encode() in lib.ce_last_error()
+    assert act(T=127) == _lib.CE_EINVAL and b"T=127" in lib.ce_last_error()
+    assert act(nc=24) == _lib.CE_EINVAL and b"multiple of 16" in lib.ce_last_error()
+    assert act(n_mels=96) == _lib.CE_EINVAL and b"96 bands" in lib.ce_last_error()
+    assert act(n=65536) == _lib.CE_EINVAL and b"n=65536" in lib.ce_last_error()
+    assert act(n=-1) == _lib.CE_EINVAL
+    assert act(ws_bytes=ws - 1) == _lib.CE_EWORKSPACE
+    assert act(mel=None) == _lib.CE_EINVAL and act(out=None) == _lib.CE_EINVAL and b"null" in lib.ce_last_error()
+    assert act(n=0, mel=None) == _lib.CE_OK  # nothing to run
+
+
+def test_member_activations_refuses_bad_arguments():
+    from ce_amd import cnn
+
+    m = cnn.DeviceShortChunkCNN.__new__(cnn.DeviceShortChunkCNN)
+    with pytest.raises(ValueError, match="HIP device"):
+        m.activations(torch.zeros(1, 128, 128), 1)
+
+
+@pytest.mark.parametrize("nc,S,T", X.EXACT_CASES)
+def test_exact_states_are_exact_and_alive(nc, S, T):
+    """What the bit-for-bit GPU comparison rests on, for every case it uses:
+    float32 equals float64 at every block and at the logits; at least 0.4 of a
+    block's activations are non-zero and they take at least 50 distinct values;
+    the HTK bank of these states has bands that hold no bin."""
+    for seed in X.EXACT_SEEDS:
+        state, mel, acts, z = X.exact_case(nc, S, T, seed)
+        with torch.no_grad():
+            a32 = R.activations(mel, state)
+            z32 = R.logits(a32[-1], state).numpy()
+        assert len(acts) == 7
+        for b, (a64, a) in enumerate(zip(acts, a32), start=1):
+            a = a.permute(0, 2, 3, 1).numpy()
+            assert a.dtype == np.float32 and a64.dtype == np.float64
+            assert a64.shape == (S, 128 >> b, T >> b, R.CH[b] * nc)
+            assert np.array_equal(a.astype(np.float64), a64), (seed, b)
+            assert np.array_equal(a64.astype(np.float32).astype(np.float64), a64), (seed, b)
+            assert np.abs(a64).max() <= 128.0
+            assert np.count_nonzero(a64) >= 0.4 * a64.size, (seed, b, np.count_nonzero(a64) / a64.size)
+            assert np.unique(a64).size >= 50, (seed, b, np.unique(a64).size)
+        assert np.array_equal(z32.astype(np.float64), z), seed
+    fb = state["spec.mel_scale.fb"].numpy()
+    assert fb.shape == (R.N_BINS, R.N_MELS) and (fb >= 0).all() and (fb.sum(0) == 0).any()
+
+
+def test_packed_exact_state_is_the_state():
+    """The record of an exact state holds the weights themselves: the folded
+    scales are the BatchNorm weights, the shifts bias + bn.bias, to the bit."""
+    from ce_amd import cnn
+
+    nc = 16
+    _, s = cnn.read_state(X.exact_state(nc, seed=0))
+    rec = cnn.pack_state(nc, s)
+    assert rec[0] == np.float32(0.5) and rec[1] == np.float32(0.25)
+    o = 16 + 9 * nc
+    assert np.array_equal(rec[o:o + nc], s["layer1.bn.weight"].astype(np.float32))
+    want = s["layer1.conv.bias"] * s["layer1.bn.weight"] + s["layer1.bn.bias"]
+    assert np.array_equal(rec[o + nc:o + 2 * nc].astype(np.float64), want)
+    assert set(np.unique(rec[16:16 + 9 * nc])) == {-1.0, 0.0, 1.0}
 
 
 def test_member_refuses_a_cpu_tensor():

@@ -8,7 +8,9 @@ the largest |dB| for the front end).  K is twice the largest ratio
 |dev - f64| / e32 measured on the first MI355X run (profiles/cnn_member.json,
 "parity"), rounded up to a power of two; only K <= 64 is acceptable.  Measured:
 the probabilities (body and end to end) 4.254 at most (nc = 128, K = 2304 terms
-in the longest chain), so K = 16; the front end 0.87, so K = 2.
+in the longest chain; nc = 48, the partial Cout tiles: 2.809), so K = 16.  The
+front end 0.87, so K = 2 (the edge inputs of tests/test_gpu_cnn_edges.py have a
+K of their own, derived there by the same rule).
 
 The users form, the exclusion and set_model are checked bit for bit against
 the one-model call."""

@@ -5,7 +5,11 @@ of 59049 samples, nc = 128, shared weights (Uw = 1) and own weights (Uw = U).
       wall-clock device time (events, median of 3 after a warm-up) of the front
       end alone and of a whole predict_proba_users pass, both forms; and the
       parity ratios |dev - f64| / e32 of the cases of tests/test_gpu_cnn.py
-      (tests/cnn_ref.py), from which the tests' K is set
+      (tests/cnn_ref.py) and of the front-end edges of
+      tests/test_gpu_cnn_edges.py (tests/cnn_exact.py), from which the tests' K
+      is set
+  python tools/cnn_member_probe.py parity OUT.json
+      the parity ratios alone (OUT.json's other entries stay)
   python tools/cnn_member_probe.py torch OUT.json
       on the same box and data: torch.nn.functional float32 forward of the same
       network (tests/cnn_ref.forward, shared weights), median of 3
@@ -100,6 +104,16 @@ def parity(R):
         state, wave, f64, f32 = R.front_case(length)
         got = ce_amd.DeviceShortChunkCNN(state).logmel(wave.cuda()).cpu().numpy()
         row("front_end_dB", {"L": length, "S": 3}, got, f64, f32, R.floor_db(f64))
+    import numpy as np
+
+    import cnn_exact as X
+
+    for name in X.FRONT_EDGES:  # the edge inputs of tests/test_gpu_cnn_edges.py, over the HTK bank
+        fb, wave, f64, f32 = X.front_edge(name)
+        got = ce_amd.DeviceShortChunkCNN(X.exact_state(16, seed=0)).logmel(wave.cuda()).cpu().numpy()
+        fin = np.isfinite(f64)  # the "nan" case: the entries off the NaN frames
+        row("front_end_edge_dB", {"case": name, "L": int(wave.shape[1]), "S": 3}, got[fin], f64[fin], f32[fin],
+            R.floor_db(f64[fin]))
     nc, S, length = R.E2E_CASE
     state, wave, f64, f32 = R.e2e_case(nc, S, length)
     got = ce_amd.DeviceShortChunkCNN(state).predict_proba(wave.cuda()).cpu().numpy()
@@ -130,6 +144,15 @@ def run(out):
         del member, wave
         torch.cuda.empty_cache()
     print(json.dumps({k: d[k] for k in ("shared_weights", "own_weights", "front_end_only")}))
+
+
+def run_parity(out):
+    import cnn_ref as R
+
+    d = load(out)
+    d["parity"] = parity(R)
+    save(out, d)
+    print(json.dumps([{**r["case"], "kind": r["kind"], "ratio": round(r["ratio"], 3)} for r in d["parity"]]))
 
 
 def run_torch(out):
@@ -195,6 +218,8 @@ if __name__ == "__main__":
     mode = sys.argv[1]
     if mode == "run":
         run(sys.argv[2])
+    elif mode == "parity":
+        run_parity(sys.argv[2])
     elif mode == "torch":
         run_torch(sys.argv[2])
     elif mode == "trace":
