@@ -47,6 +47,34 @@ def test_restatement_equals_sklearn(D, C):
     assert g.class_count_[C - 1] > 0
 
 
+@pytest.mark.parametrize("C", [2, 4, 8])
+@pytest.mark.parametrize("D", [2, 65, 260, 512])
+def test_restatement_equals_sklearn_past_the_row_tile(D, C):
+    """Chained batches of 1024, 1025, 2049 and 3000 rows (the device kernel stages
+    1024 rows at a time; tests/test_gpu_fit_batch_edges.py compares it with the
+    restatement there): the last class unseen until the second batch, where it
+    holds row 1024 alone."""
+    pytest.importorskip("sklearn")
+    from sklearn.naive_bayes import GaussianNB
+
+    rng = np.random.default_rng(7000 * D + C)
+    X0, y0 = rng.normal(size=(3 * C, D)), np.arange(3 * C) % (C - 1)
+    g = GaussianNB().partial_fit(X0, y0, classes=np.arange(C))
+    assert g.class_count_[C - 1] == 0
+    th, va, cc = g.theta_.copy(), g.var_.copy(), g.class_count_.copy()
+    for B in (1024, 1025, 2049, 3000):
+        X = rng.normal(size=(B, D)) * np.exp(rng.normal(0, 1, D))
+        y = rng.integers(0, C - 1, B) if B <= 1025 else rng.integers(0, C, B)
+        if B == 1025:
+            y[1024] = C - 1
+        g.partial_fit(X, y)
+        th, va, cc, prior, eps = gnb_partial_fit(X, y, th, va, cc)
+        assert_state((th, va, cc, prior, eps), (g.theta_, g.var_, g.class_count_, g.class_prior_, g.epsilon_), (D, C, B))
+        if B <= 1025:
+            assert cc[C - 1] == B - 1024  # unseen, then its one row
+    assert g.class_count_[C - 1] > 1
+
+
 def test_restatement_nan_cell():
     """One NaN cell: epsilon is NaN and var is all NaN, in sklearn and in the restatement."""
     pytest.importorskip("sklearn")

@@ -86,6 +86,30 @@ def test_restatement_equals_sklearn(D, C):
             assert same_bits(coef, m.coef_) and same_bits(b, m.intercept_) and t == m.t_, (D, C, alpha, n)
 
 
+@pytest.mark.parametrize("C", [4, 8])
+def test_restatement_equals_sklearn_past_128_rows_at_full_width(C):
+    """D = 260: chained batches of 129 and 257 rows (the device kernel fetches the
+    visiting order's rows in blocks of 64; tests/test_gpu_fit_batch_edges.py
+    compares it with the restatement there).  The D = 260 chains above stop at 40 rows."""
+    sklearn = pytest.importorskip("sklearn")
+    if sklearn.__version__ != PINNED:
+        pytest.skip(f"the restatement is pinned to sklearn {PINNED} (installed: {sklearn.__version__})")
+    from sklearn.linear_model import SGDClassifier
+
+    warnings.simplefilter("ignore")
+    rng = np.random.default_rng(260 + C)
+    D, rs = 260, 31 + C
+    m = SGDClassifier(loss="log_loss", penalty="l2", random_state=rs, warm_start=True, alpha=1e-4)
+    m.fit(rng.normal(size=(5 * C, D)), np.arange(5 * C) % C)
+    coef, b, t = m.coef_.copy(), m.intercept_.copy(), float(m.t_)
+    for n in (129, 257):
+        X, y = rng.normal(size=(n, D)), rng.integers(0, C, n)
+        m.partial_fit(X, y)
+        coef, b, t, finite = sgd_partial_fit(X, y, coef, b, t, 1e-4, rs)
+        assert finite
+        assert same_bits(coef, m.coef_) and same_bits(b, m.intercept_) and t == m.t_, (C, n)
+
+
 def test_restatement_overflow_is_where_sklearn_raises():
     sklearn = pytest.importorskip("sklearn")
     if sklearn.__version__ != PINNED:
