@@ -732,14 +732,20 @@ def test_segment_mean_vs_restatement(ce, dt, grouped):
 def test_segment_mean_tiles_large(ce, C, dt):
     """The LDS-DMA tile kernel (k_segment_mean_tiles: grouped dense rows, taken
     once every wave runs >= 4 steps) at 300k ragged songs (1..15 frames, 1 % of
-    them 40, spanning tiles): NaN cells, all-NaN songs, bit-exact vs the restatement,
-    into a strided f64 stack slot too."""
+    them 40): NaN cells, all-NaN songs, bit-exact vs the restatement, into a
+    strided f64 stack slot too.  A step of 64 / C songs of these lengths stays
+    inside one 16 KiB tile (TR = 16384 / (C * itemsize) rows), so a dozen songs
+    of TR + 1 .. 3 TR rows are added: their steps take two to four tiles (the
+    layouts around the tile edge are in test_gpu_frames_tiles.py)."""
     from oracle.ce_oracle import ref_group_mean
 
     rng = np.random.default_rng(C + (dt == np.float32))
     N = 300_000
     sizes = rng.integers(1, 16, N)
-    sizes[rng.random(N) < 0.01] = 40  # a few long songs span tiles
+    sizes[rng.random(N) < 0.01] = 40
+    TR = 16384 // (C * np.dtype(dt).itemsize)
+    sizes[rng.choice(N, 12, replace=False)] = rng.integers(TR + 1, 3 * TR + 1, 12)  # longer than a tile
+    assert (sizes > TR).sum() == 12
     s_id = np.repeat(np.arange(N), sizes)
     F = len(s_id)
     vals = rng.random((F, C)).astype(dt)
